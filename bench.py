@@ -11,6 +11,12 @@ no checkpoint), all physics/env inputs resident in HBM.
 Multi-GPU: one process per GPU (torch.distributed.run), envs sharded (4096 per rank, weak
 scaling), policy gradients all-reduced with RCCL (backend "nccl") once per minibatch.
 
+A plain run sets up, warms up, times the --steps iterations and prints the result line (metric,
+value, ms_per_step, the configuration and the last iteration's collection / learn times);
+--dump-outputs DIR also writes what the last timed iteration computed.  Everything below — the
+roofline object, the data-parallel all-reduce timing and the CPU baselines — is measured and
+added to the line only with --full.
+
 The roofline object is for the dominant kernel, K_step (FP32 bound, VALU + f32 MFMA: state lives
 in registers/LDS across the 10 substeps, algorithmic HBM traffic ~1.8 KB/env-step); its launch
 time is measured with HIP events recorded on the stream the kernel runs on (torch's current
@@ -250,6 +256,30 @@ def cpu_baseline(n_envs=256, T=24, threads=None, iterations=3):
     return n_envs * T * iterations / dt, threads, dt
 
 
+def roofline_report(env, timer, args, c5):
+    """K_step's roofline object (module docstring) from the timed region's sampled launches."""
+    rows = active_rows(env)
+    traffic, traffic_src = (pmc_traffic("k_step") if args.envs == 4096 and args.terrain == "plane" and not c5
+                            else (None, None))
+    ms_step = timer.mean_ms("k_step")
+    flops = physics_flops_per_env_step(rows) * args.envs
+    achieved_tflops = flops / (ms_step * 1e-3) / 1e12
+    return {"kernel": "k_step", "bound": "fp32-valu", "pipe": "fp32 VALU + f32 MFMA (W = Z^T Z); f32 MFMA peak = f32 vector peak",
+            "achieved": round(achieved_tflops, 4), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": round(achieved_tflops / FP32_PEAK_TFLOPS, 6), "traffic": traffic,
+            "traffic_unit": "bytes/launch (HBM, PMC)", "traffic_source": traffic_src,
+            "algorithmic_bytes_per_launch": KSTEP_BYTES_PER_ENV * args.envs,
+            "hbm_achieved_GBs": round(KSTEP_BYTES_PER_ENV * args.envs / (ms_step * 1e-3) / 1e9, 1),
+            "hbm_frac": round(KSTEP_BYTES_PER_ENV * args.envs / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+            "valu_issue_util": sq_issue(),
+            "valu_issue_source": f"profiles/{PROFILE_DIR}/sq_counters_k_step.json (2 x SQ_ACTIVE_INST_VALU / SQ_WAVE_CYCLES)",
+            "avg_launch_ms": round(ms_step, 4), "launches": timer.count("k_step"),
+            "launch_sampling": f"HIP events on 1 in {timer.every} launches of the timed region",
+            "flops_per_launch": flops, "active_rows_per_env": round(rows, 2),
+            "mfma": mfma_stats(rows, args.envs),
+            "k_post_avg_ms": round(timer.mean_ms("k_post"), 4)}
+
+
 def comm_report(runner, timer, world, rank_ms):
     """The data-parallel exchange of one iteration (None at world size 1): the per-minibatch
     flat-gradient (+ KL slot) all-reduce and the advantage-statistics all-reduce, each timed with
@@ -272,6 +302,52 @@ def comm_report(runner, timer, world, rank_ms):
             "allreduce_samples": timer.count("allreduce"),
             "timing": f"HIP events on this rank's current stream, 1 in {timer.every} calls of the timed region",
             "rank_ms_per_step": rank_ms}
+
+
+DUMP_BUDGET_BYTES = 60 * 2 ** 20  # --dump-outputs writes at most this much in all
+
+
+def sample_to_budget(arrays, budget=DUMP_BUDGET_BYTES, small=2 ** 20):
+    """`arrays` as they are when they fit `budget` bytes in all; otherwise every array above
+    `small` bytes cut to a sorted sample of its flattened elements (the same fraction of each,
+    drawn with a fixed seed: the same elements in every run), the others whole."""
+    fixed = sum(a.nbytes for a in arrays.values() if a.nbytes <= small)
+    large = sum(a.nbytes for a in arrays.values() if a.nbytes > small)
+    if fixed + large <= budget:
+        return dict(arrays)
+    keep = max(0.0, (budget - fixed) / large)
+    out = {}
+    for name, a in arrays.items():
+        if a.nbytes > small:
+            idx = np.sort(np.random.default_rng(5).choice(a.size, int(a.size * keep), replace=False))
+            a = a.reshape(-1)[idx]
+        out[name] = a
+    return out
+
+
+def dump_outputs(runner, env, out_dir):
+    """--dump-outputs: what the last timed PPO iteration left with the caller of
+    OnPolicyRunner.learn, as float32 out_dir/<name>.npy — the updated policy parameters, the
+    iteration's loss means, the last rollout's storage slots (actions, rewards, dones, values,
+    returns, normalised advantages) and the env's state and observation buffers after its last
+    step.  The run is seeded and bitwise reproducible (tests/test_gpu_parity.py), so two builds
+    given the same arguments can be compared array by array.  When the arrays exceed the budget
+    (more envs than the default), every array above 1 MiB is cut to the same fixed, seeded sample
+    of its elements."""
+    st, ac = runner.alg.storage, runner.alg.actor_critic
+    stats = runner.last_iteration_stats
+    tensors = {"policy_params": torch.cat([p.detach().reshape(-1).float() for _, p in ac.named_parameters()]),
+               "losses": torch.tensor([stats[k] for k in ("value_loss", "surrogate_loss", "lin_vel_loss")]),
+               "obs": env.get_observations(), "privileged_obs": env.get_privileged_observations(),
+               "rewards": env.rew_buf, "resets": env.reset_buf,
+               "root_states": env.root_states, "dof_pos": env.dof_pos, "dof_vel": env.dof_vel,
+               "torques": env.torques, "contact_forces": env.contact_forces,
+               "rollout_actions": st.actions, "rollout_rewards": st.rewards, "rollout_dones": st.dones,
+               "rollout_values": st.values, "rollout_returns": st.returns, "rollout_advantages": st.advantages}
+    arrays = {k: t.detach().to("cpu", torch.float32).numpy() for k, t in tensors.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in sample_to_budget(arrays).items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def _free_port():
@@ -322,12 +398,18 @@ def main():
                     help="launcher / rank-bookkeeping check only (no GPU work, gloo)")
     ap.add_argument("--steps", type=int, default=10, help="timed PPO iterations")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also report what the headline figure does not need: K_step's roofline (HIP-event "
+                         "timing of sampled launches inside the timed region), the data-parallel all-reduce "
+                         "timing and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--T", type=int, default=24, help="rollout length (num_steps_per_env)")
     ap.add_argument("--cpu-envs", type=int, default=4096, help="CPU baseline sample on all host threads")
     ap.add_argument("--cpu-envs-1core", type=int, default=256, help="CPU baseline sample on one thread")
     ap.add_argument("--cpu-iterations", type=int, default=3, help="PPO iterations of the CPU baseline samples")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--no-gemm-table", action="store_true", help="hipBLASLt default GEMM heuristics")
     ap.add_argument("--terrain", default="plane", choices=["plane", "heightfield"],
                     help="plane = config 2; heightfield = config 3 (2100x2100 generated terrain)")
@@ -380,23 +462,29 @@ def main():
                    num_envs_total=world * args.envs)
     runner = OnPolicyRunner(env, train_cfg(args.T, "bf16" if c5 else "fp32", "fp16" if c5 else "fp32"),
                             log_dir=None, device=device)
-    timer = KernelTimer(every=int(os.environ.get("HG_TIMER_EVERY", "4")))
-    env.kernel_timer = timer
-    if world > 1:  # the eager data-parallel all-reduces (gradients + KL per minibatch, advantage stats)
-        runner.alg.comm_timer = timer
-        runner.alg.storage.comm_timer = timer
+    timer = None
+    if args.full:  # HIP events around sampled launches of the timed region (the roofline and comm figures)
+        timer = KernelTimer(every=int(os.environ.get("HG_TIMER_EVERY", "4")))
+        env.kernel_timer = timer
+        if world > 1:  # the eager data-parallel all-reduces (gradients + KL per minibatch, advantage stats)
+            runner.alg.comm_timer = timer
+            runner.alg.storage.comm_timer = timer
     runner.learn(args.warmup, init_at_random_ep_len=True)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    timer.enabled = timer.every > 0
+    if timer is not None:
+        timer.enabled = timer.every > 0
     t0 = time.time()
     runner.learn(args.steps)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.time() - t0
-    timer.enabled = False
+    if timer is not None:
+        timer.enabled = False
+    if args.dump_outputs:
+        dump_outputs(runner, env, args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, f"rank{rank}"))
     rank_ms = None
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
@@ -407,26 +495,6 @@ def main():
         elapsed = t.item()
     env_steps = args.envs * args.T * args.steps * world
     value = env_steps / elapsed
-    rows = active_rows(env)
-    traffic, traffic_src = (pmc_traffic("k_step") if args.envs == 4096 and args.terrain == "plane" and not c5
-                            else (None, None))
-    ms_step = timer.mean_ms("k_step")
-    flops = physics_flops_per_env_step(rows) * args.envs
-    achieved_tflops = flops / (ms_step * 1e-3) / 1e12
-    roofline = {"kernel": "k_step", "bound": "fp32-valu", "pipe": "fp32 VALU + f32 MFMA (W = Z^T Z); f32 MFMA peak = f32 vector peak",
-                "achieved": round(achieved_tflops, 4), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": round(achieved_tflops / FP32_PEAK_TFLOPS, 6), "traffic": traffic,
-                "traffic_unit": "bytes/launch (HBM, PMC)", "traffic_source": traffic_src,
-                "algorithmic_bytes_per_launch": KSTEP_BYTES_PER_ENV * args.envs,
-                "hbm_achieved_GBs": round(KSTEP_BYTES_PER_ENV * args.envs / (ms_step * 1e-3) / 1e9, 1),
-                "hbm_frac": round(KSTEP_BYTES_PER_ENV * args.envs / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                "valu_issue_util": sq_issue(),
-                "valu_issue_source": f"profiles/{PROFILE_DIR}/sq_counters_k_step.json (2 x SQ_ACTIVE_INST_VALU / SQ_WAVE_CYCLES)",
-                "avg_launch_ms": round(ms_step, 4), "launches": timer.count("k_step"),
-                "launch_sampling": f"HIP events on 1 in {timer.every} launches of the timed region",
-                "flops_per_launch": flops, "active_rows_per_env": round(rows, 2),
-                "mfma": mfma_stats(rows, args.envs),
-                "k_post_avg_ms": round(timer.mean_ms("k_post"), 4)}
     result = {
         "metric": "env-steps/sec (whole node) at 4096 envs + PPO iters/sec, 1/2/4/8 MI355X",
         "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -448,12 +516,13 @@ def main():
                             "accumulation; error per element below torch's f32 GEMM's, tests/test_gpu_gemm.py), "
                             "the other products on f32 MFMA (own kernels) or hipBLASLt f32"
                             if not c5 else "bf16 policy (config 5)")},
-        "roofline": roofline,
-        "comm": comm_report(runner, timer, world, rank_ms),
         "collection_time_s": round(runner.last_iteration_stats.get("collection_time", float("nan")), 4),
         "learn_time_s": round(runner.last_iteration_stats.get("learn_time", float("nan")), 4),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        result["roofline"] = roofline_report(env, timer, args, c5)
+        result["comm"] = comm_report(runner, timer, world, rank_ms)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # config 2 on all host cores for >= 3 iterations (the headline
         # baseline), the same on one core over a smaller sample, and config 1 (4 envs, 1 iteration)
         it = args.cpu_iterations

@@ -10,5 +10,7 @@ if [ -f build/kprobe/libhgsim.so ]; then
   timeout -k 10 300 python scripts/dev/kstep_probe.py run > gpurun_out/kstep_phase_probe.txt 2>&1 || { echo "probe failed"; tail -5 gpurun_out/kstep_phase_probe.txt; exit 1; }
   grep -v amdgpu.ids gpurun_out/kstep_phase_probe.txt
 fi
-timeout -k 10 300 python bench.py > gpurun_out/kstep_bench.json 2> gpurun_out/kstep_bench.err || { tail -20 gpurun_out/kstep_bench.err; exit 1; }
-python -c "import json;d=json.loads(open('gpurun_out/kstep_bench.json').read().strip().splitlines()[-1]);print(d['value'],d['ms_per_step'],d.get('roofline'))"
+# --full: the line's roofline object holds K_step's time per launch
+B="${BENCH_OUT:-$(mktemp -d)}"
+timeout -k 10 300 python bench.py --full > "$B/kstep_bench.json" 2> "$B/kstep_bench.err" || { tail -20 "$B/kstep_bench.err"; exit 1; }
+python -c "import json,sys;d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]);print(d['value'],d['ms_per_step'],d.get('roofline'))" "$B/kstep_bench.json"

@@ -9,5 +9,7 @@ bash scripts/pmc_sq.sh || exit $?
 python scripts/sq_summary.py gpurun_out/pmc_sq gpurun_out/pmc_sq/sq_counters_k_step.json || exit $?
 cd "$R"
 timeout -k 10 700 python scripts/trajectory_curve.py > gpurun_out/traj.log 2>&1 || exit $?
-timeout -k 10 600 python bench.py > gpurun_out/bench_round.log 2>&1 || exit $?
-tail -1 gpurun_out/bench_round.log
+# the bench line with its roofline object and CPU baselines (BENCH_LOG: where the run's output is kept)
+BENCH_LOG="${BENCH_LOG:-$(mktemp -d)/bench_round.log}"
+timeout -k 10 600 python bench.py --full > "$BENCH_LOG" 2>&1 || exit $?
+tail -1 "$BENCH_LOG"

@@ -3,7 +3,6 @@ and the ONNX actor wire format (humanoid/OnnxTest.onnx: Gemm/Elu, input -> outpu
 import os
 
 import numpy as np
-import pytest
 import torch
 
 from humanoid.algo.ppo import ActorCritic
@@ -43,18 +42,28 @@ def test_onnx_roundtrip(tmp_path):
         torch.testing.assert_close(ac2.act_inference(x), ac.act_inference(x), rtol=0, atol=0)
 
 
-REF_ONNX = "/root/reference/humanoid/OnnxTest.onnx"
-
-
-@pytest.mark.skipif(not os.path.exists(REF_ONNX), reason="reference tree not present (GPU box)")
-def test_reads_reference_onnx():
-    """The reference's shipped ONNX actor parses into a Gemm/Elu chain (data only; nothing in the
-    file is executed)."""
-    g = read_onnx_graph(REF_ONNX)
+def test_reads_reference_actor_onnx(golden, tmp_path):
+    """The reference's trained actor (its weights: tests/golden/onnx_actor.npz), written in the
+    ONNX actor wire format, parses into a Gemm/Elu chain that evaluates to what the graph's
+    initializers give in numpy.  The weights are the fixture's; the file around them is this
+    build's (the reference's own file is not part of the repository)."""
+    w = golden("onnx_actor.npz")
+    ac = ActorCritic(**DIMS)
+    with torch.no_grad():
+        for k, lin in enumerate(l for l in ac.actor if isinstance(l, torch.nn.Linear)):
+            lin.weight.copy_(torch.from_numpy(w[f"W{k}"]))
+            lin.bias.copy_(torch.from_numpy(w[f"b{k}"]))
+    onnx_path = export_policy_as_onnx(ac, str(tmp_path))
+    g = read_onnx_graph(onnx_path)
     ops = [n["op_type"] for n in g["nodes"]]
     assert set(ops) <= {"Gemm", "Elu"} and ops[0] == "Gemm" and ops[-1] == "Gemm"
-    m = load_onnx_mlp(REF_ONNX)
+    m = load_onnx_mlp(onnx_path)
     lin = [l for l in m if isinstance(l, torch.nn.Linear)]
+    assert [tuple(l.weight.shape) for l in lin] == [w[f"W{k}"].shape for k in range(4)]
+    for k, l in enumerate(lin):
+        np.testing.assert_array_equal(l.weight.detach().numpy(), w[f"W{k}"])
+        np.testing.assert_array_equal(l.bias.detach().numpy(), w[f"b{k}"])
+    torch.manual_seed(2)
     x = torch.randn(3, lin[0].in_features)
     with torch.no_grad():
         y = m(x)
