@@ -50,7 +50,7 @@ int soa_rows(int id) {
     case HG_T_COMMANDS: return 4;
     case HG_T_REW_BUF: case HG_T_RESET_BUF: case HG_T_TIME_OUT_BUF: case HG_T_EPISODE_LENGTH:
     case HG_T_ENV_FRICTION: case HG_T_BODY_MASS: case HG_T_NONFINITE: case HG_T_TERRAIN_LEVEL:
-    case HG_T_TERRAIN_TYPE: case HG_T_ROWS_DROPPED: return 1;
+    case HG_T_TERRAIN_TYPE: case HG_T_ROWS_DROPPED: case HG_T_ENV_ROWS: case HG_T_ENV_ORDER: return 1;
     case HG_T_EPISODE_SUMS: return HG_NUM_REWARDS;
     case HG_T_FEET_AIR_TIME: case HG_T_LAST_CONTACTS: case HG_T_FEET_HEIGHT: case HG_T_LAST_FEET_Z: return 2;
     case HG_T_PUSH_FORCE: case HG_T_PUSH_TORQUE: case HG_T_BASE_LIN_VEL: case HG_T_BASE_ANG_VEL:
@@ -63,7 +63,8 @@ int dtype_of(int id) {
   switch (id) {
     case HG_T_RESET_BUF: case HG_T_TIME_OUT_BUF: case HG_T_LAST_CONTACTS: return 2;
     case HG_T_EPISODE_LENGTH: return 1;
-    case HG_T_NONFINITE: case HG_T_TERRAIN_LEVEL: case HG_T_TERRAIN_TYPE: case HG_T_ROWS_DROPPED: return 3;
+    case HG_T_NONFINITE: case HG_T_TERRAIN_LEVEL: case HG_T_TERRAIN_TYPE: case HG_T_ROWS_DROPPED:
+    case HG_T_ENV_ROWS: case HG_T_ENV_ORDER: return 3;
     default: return 0;
   }
 }
@@ -87,6 +88,7 @@ Layout make_layout(const hg_cfg* c) {
     // EP_STATS region: [24] stats, [24] accumulators, then the [HG_EP_RING, 24] snapshot ring
     if (id == HG_T_EP_STATS) { o += align256((48 + HG_EP_RING * 24) * sizeof(float)); continue; }
     if (id == HG_T_EP_STATS_RING) { L.off[id] = L.off[HG_T_EP_STATS] + 48 * sizeof(float); continue; }
+    if (id == HG_T_ENV_ROWS || id == HG_T_ENV_ORDER) continue;  // views of the env_rows / env_order regions below
     o += align256((size_t)soa_rows(id) * np * esize(dtype_of(id)));
   }
   // the observation histories: one sliding window per env row (hg_obs_window_frames)
@@ -104,6 +106,8 @@ Layout make_layout(const hg_cfg* c) {
   L.env_order = o; o += align256((size_t)np * 4);
   L.off[HG_T_OBS_BUF] = L.obs_buf;
   L.off[HG_T_PRIV_BUF] = L.priv_buf;
+  L.off[HG_T_ENV_ROWS] = L.env_rows;
+  L.off[HG_T_ENV_ORDER] = L.env_order;
   L.bytes = o;
   return L;
 }
@@ -336,7 +340,11 @@ static int do_post(Sim* s, uint64_t counter, int mode, const uint8_t* mask, void
   const int old = s->head;
   const int shift = old + 1 >= hw;  // slots old + 1 .. old + F - 1 move to 0 .. F - 2
   const int head = shift ? 0 : old + 1;
-  const float inv_len_s = 1.0f / ((float)s->cfg.max_episode_length * s->cfg.dt);
+  // extras["episode"] divides by cfg.env.episode_length_s itself (humanoid_env.py:1143), which is
+  // not max_episode_length * dt when the length is no multiple of dt (the step count is its ceil)
+  const float len_s = s->cfg.max_episode_length_s > 0.f ? s->cfg.max_episode_length_s
+                                                        : (float)s->cfg.max_episode_length * s->cfg.dt;
+  const float inv_len_s = 1.0f / len_s;
   const int slot = (int)(s->post_seq % HG_EP_RING);
   const HgWindow wo = {(float*)(s->arena + s->L.obs_buf), (int64_t)win_frames(s->cfg.frame_stack, &s->cfg) * HG_OBS1,
                        HG_OBS1, s->cfg.frame_stack, head, shift ? old + 1 : -1};

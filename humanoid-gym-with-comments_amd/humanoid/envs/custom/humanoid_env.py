@@ -315,6 +315,10 @@ class XBotLFreeEnv(BaseTask):
         # constraint rows / contact points the solver's row budget dropped, per env, summed over
         # substeps (diagnostic; 0 in normal operation)
         self.rows_dropped = self._view(T["ROWS_DROPPED"])
+        # K_step's wave-balancing state (read-only diagnostics): each env's constraint rows in the
+        # latest step, and the env each half-wave runs next (a permutation within every XCD range)
+        self.env_rows = self._view(T["ENV_ROWS"])
+        self.env_order = self._view(T["ENV_ORDER"])
 
     def _global_ids(self):
         """(offset, total): this shard's envs are global ids [offset, offset + num_envs) of total."""

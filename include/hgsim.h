@@ -134,7 +134,9 @@ typedef struct hg_cfg {
   int32_t curriculum;
   int32_t terrain_rows, terrain_cols;   /* levels x types of terrain_origins */
   float terrain_env_length;             /* move up when the robot walked > length / 2 */
-  float max_episode_length_s;           /* move down when it walked < |cmd_xy| * T_ep / 2 */
+  float max_episode_length_s;           /* env.episode_length_s: move down when it walked < |cmd_xy| * T_ep / 2;
+                                         * divisor of the episode reward means (HG_T_EP_STATS; <= 0:
+                                         * max_episode_length * dt) */
   int32_t env_offset;                   /* global id of this shard's env 0 (data parallel): every Philox
                                          * draw is keyed by the global env id */
   const float* terrain_origins;         /* device [rows, cols, 3], caller-owned */
@@ -183,6 +185,10 @@ enum hg_tensor_id {
                             without a copy launch */
   HG_T_ROWS_DROPPED,     /* [N] int32: constraint rows / contact points the row budget dropped, summed over substeps;
                          * zero at hg_create, CUMULATIVE afterwards (resets do not clear it: zero it before a run) */
+  HG_T_ENV_ROWS,         /* [N] int32, read-only diagnostic: constraint rows of each env in the latest hg_step (the
+                            wave-balancing sort key) */
+  HG_T_ENV_ORDER,        /* [N] int32, read-only diagnostic: the env K_step's half-wave k runs, as the latest post
+                            launch sorted it (a permutation of each XCD's env range; identity without balancing) */
   HG_T_COUNT
 };
 

@@ -129,6 +129,34 @@ def test_gae_kernel_large_properties():
     np.testing.assert_array_equal(st.returns[..., 0].cpu().numpy(), ret)
 
 
+def test_gae_ragged_size_matches_oracle():
+    """T = 5, N = 333: the second 256-env scan block is partial, and T N = 1665 = 1 mod 4 reaches
+    k_gae_norm's scalar tail after its float4 body (T = 24 never does).  Returns bitwise against
+    the oracle; normalised advantages against the float64 (A - mean) / (std_unbiased + 1e-8) of the
+    oracle's raw advantages, at the golden test's tolerance."""
+    _need_gpu()
+    import envlogic_ref as E
+    from humanoid.algo.ppo import RolloutStorage
+    T, N = 5, 333
+    rs = np.random.RandomState(17)
+    r = rs.standard_normal((T, N)).astype(np.float32)
+    v = rs.standard_normal((T, N)).astype(np.float32)
+    d = (rs.uniform(size=(T, N)) < 0.1).astype(np.uint8)
+    last = rs.standard_normal(N).astype(np.float32)
+    st = RolloutStorage(N, T, [1], [1], [1], device="cuda:0")
+    st.rewards.copy_(torch.from_numpy(r)[..., None])
+    st.values.copy_(torch.from_numpy(v)[..., None])
+    st.dones.copy_(torch.from_numpy(d)[..., None])
+    st.compute_returns(torch.from_numpy(last)[:, None].cuda(), 0.994, 0.9)
+    ret, raw = E.gae(r, d, v, last, 0.994, 0.9, normalize=False)
+    np.testing.assert_array_equal(st.returns[..., 0].cpu().numpy(), ret)
+    a = raw.astype(np.float64)
+    want = (a - a.mean()) / (a.std(ddof=1) + 1e-8)
+    got = st.advantages[..., 0].cpu().numpy()
+    assert got.shape == (T, N) and d.any() and d[:, 256:].any()
+    np.testing.assert_allclose(got, want, rtol=1e-5, atol=2e-6)
+
+
 def test_gae_deterministic():
     """Two identical compute_returns calls give bitwise-identical normalised advantages: the
     (sum A, sum A^2) statistics are block partials summed in a fixed order (no float atomics)."""
@@ -164,10 +192,71 @@ def _post_once(env, counter):
     torch.cuda.synchronize()
 
 
+def _plant_episode_sums(env, seed):
+    """Seeded per-env, per-term episode sums in [-0.3, 0.7] (as tests/golden/gen_goldens.py plants
+    them for the reference) written through the env's views: a statistic built from the wrong
+    term or the wrong env then differs."""
+    vals = (np.random.RandomState(seed).rand(*env._sums.shape) - 0.3).astype(np.float32)
+    env._sums.copy_(torch.from_numpy(vals).to(env._sums.device))
+    torch.cuda.synchronize()
+    return vals
+
+
+def _episode_scaled_terms(cfg, terms):
+    """The per-term episode-sum increments of one post, as envlogic_ref.total_reward adds them:
+    term x cfg.scales[term] in float32 (dt is already folded into cfg.scales)."""
+    return {n: (terms[n] * np.float32(cfg.scales[n])).astype(np.float32) for n in cfg.scales}
+
+
+def _check_episode_stats(env, sums, rid, oracle_means, label=""):
+    """extras["episode"] / HG_T_EP_STATS of the latest post or reset launch against the episode
+    sums `sums` ({term: [N] float32}, as they stood when envs `rid` were reset).
+
+    The GPU adds the m = len(rid) float32 sums of a term in block-partial order, the blocks by float
+    atomics in any order, then divides by m and multiplies by 1 / episode_length_s: m - 1 + 4
+    roundings of at most 2^-24 relative, each on a partial sum no larger than sum |s_i|.  Against the
+    float64 mean / episode_length_s that is |d| <= (m + 4) 2^-24 sum |s_i| / (m episode_length_s) per
+    term, no absolute floor.  The oracle's own float32 mean (pipeline_ref.reset_envs, pinned to the
+    reference on the CPU by tests/test_oracle_pipeline.py) is asserted to lie inside the same bound.
+    Counts compare exactly; the published dict is exactly the statistics row."""
+    from humanoid.envs.custom.humanoid_env import REWARD_NAMES
+    m = len(rid)
+    assert m > 0
+    len_s = float(env.cfg.env.episode_length_s)
+    stats = env._ep_stats.detach().cpu().numpy().copy()
+    assert stats[22] == m and stats[23] == 1.0, (label, stats[22:], m)
+    episode = env.extras["episode"]
+    assert sorted(episode) == sorted("rew_" + n for n in env.reward_names)
+    worst = 0.0
+    for k, name in enumerate(REWARD_NAMES):
+        s = sums[name][rid].astype(np.float64)
+        want = s.mean() / len_s
+        bound = (m + 4) * 2.0 ** -24 * np.abs(s).sum() / (m * len_s)
+        assert abs(float(oracle_means[name]) - want) <= bound, (label, name, "oracle", float(oracle_means[name]), want, bound)
+        got = float(stats[k])
+        if bound > 0:
+            worst = max(worst, abs(got - want) / bound)
+        assert abs(got - want) <= bound, (label, name, got, want, bound, m)
+        if "rew_" + name in episode:
+            assert float(episode["rew_" + name]) == got, (label, name)
+    print(f"episode means {label}: {m} envs reset, largest |gpu - f64| / bound over the 22 terms {worst:.3g}")
+
+
 def test_post_parity(env):
-    """K_post (rewards, commands, push, termination, masked reset, obs + noise, stacking) vs
-    the numpy pipeline on the identical GPU state, with forced resets/timeouts/resample/push."""
+    """K_post (rewards, commands, push, termination, masked reset, obs + noise, stacking, episode
+    statistics) vs the numpy pipeline on the identical GPU state, with forced
+    resets/timeouts/resample/push."""
     _post_parity(env)
+
+
+@pytest.mark.parametrize("which", ["plane", "heightfield"])
+def test_post_parity_ragged_77_envs(which):
+    """K_post at 77 envs: 5 blocks over the XCD split, the last with 13 of its 16 lanes valid (the
+    scalar frame copy, the statistics fold over nv < PEB lanes whose padding lanes hold env 76's
+    values), resets forced on envs 64 and 76 of that block."""
+    _need_gpu()
+    over = dict(terrain__mesh_type="heightfield") if which == "heightfield" else {}
+    _post_parity(_make_env(77, **over))
 
 
 def test_post_parity_heightfield(terrain_env):
@@ -181,18 +270,36 @@ def _post_parity(env, steps=3):
         env.step(torch.randn(env.num_envs, 12, device="cuda:0") * 0.5)
     torch.cuda.synchronize()
     # force the branches: base contact on some envs, timeouts, command resample
-    env.contact_forces[0:4, 0, 2] = 50.0
+    # the last env and the first env of the last K_post block (16 envs per block) too
+    n = env.num_envs
+    forced = sorted({0, 1, 2, 3, n - 1, (n - 1) // 16 * 16} & set(range(n)))
+    env.contact_forces[forced, 0, 2] = 50.0
     env.episode_length_buf[4:8] = 2400
     env.episode_length_buf[8:12] = 799
+    planted = _plant_episode_sums(env, 1000 + n)
     counter = 400 * 3  # push step
     S, hist_o, hist_p = snapshot(env)
     cfg = _oracle_cfg(env)
-    obs, priv, rew, reset, timeout, terms = PR.post(cfg, S, counter, hist_o, hist_p)
+    extras = {}
+    obs, priv, rew, reset, timeout, terms = PR.post(cfg, S, counter, hist_o, hist_p, extras=extras)
     _post_once(env, counter)
+    env._publish_extras()
     gpu = lambda t: t.detach().cpu().numpy()  # noqa: E731
     np.testing.assert_array_equal(gpu(env.reset_buf), reset)
     np.testing.assert_array_equal(gpu(env.time_out_buf), timeout)
-    assert reset[:8].all() and not reset[8:12].any()
+    np.testing.assert_array_equal(gpu(env.extras["time_outs"]), timeout)
+    assert reset[:8].all() and not reset[8:12].any() and reset[forced].all()
+    # episode statistics of the resetting envs: the sums as this post's rewards left them (the
+    # oracle's increments on the planted values; where no reset cleared them they must be the
+    # oracle's own sums bit for bit)
+    names = __import__("envlogic_ref").REWARD_NAMES
+    rid, keep = np.nonzero(reset)[0], np.nonzero(~reset.astype(bool))[0]
+    inc = _episode_scaled_terms(cfg, terms)
+    after = {nm: (planted[k] + inc[nm]).astype(np.float32) for k, nm in enumerate(names)}
+    for k, nm in enumerate(names):
+        np.testing.assert_array_equal(after[nm][keep], S["episode_sums"][nm][keep], err_msg=nm)
+        assert (gpu(env._sums[k])[rid] == 0).all() and (S["episode_sums"][nm][rid] == 0).all(), nm
+    _check_episode_stats(env, after, rid, extras["episode"], label=f"post n={n}")
     np.testing.assert_allclose(gpu(env.rew_buf), rew, rtol=2e-4, atol=2e-5)
     np.testing.assert_allclose(gpu(env.commands), S["commands"], rtol=1e-5, atol=1e-5)
     np.testing.assert_allclose(gpu(env.root_states), S["root_states"], rtol=1e-6, atol=1e-6)
@@ -1159,15 +1266,21 @@ def test_reset_idx_and_indexed_writes():
     for _ in range(4):
         env.step(torch.randn(env.num_envs, 12, device="cuda:0") * 0.3)
     torch.cuda.synchronize()
+    _plant_episode_sums(env, 77)
     S, _, _ = snapshot(env)
     g = lambda t: t.detach().cpu().numpy()  # noqa: E731
     S["projected_gravity"] = g(env.projected_gravity)
     ids = np.array([1, 5, 9, 33])
     R = copy.deepcopy(S)
-    PR.reset_envs(_oracle_cfg(env), R, ids, env.common_step_counter)
+    means = PR.reset_envs(_oracle_cfg(env), R, ids, env.common_step_counter)
     env.reset_idx(torch.tensor(ids, device="cuda:0"))
     torch.cuda.synchronize()
     keep = np.setdiff1d(np.arange(env.num_envs), ids)
+    # the reset launch's episode statistics (k_post mode 1: one float atomic per env and term)
+    _check_episode_stats(env, S["episode_sums"], ids, means, label="reset_idx")
+    for k, nm in enumerate(__import__("envlogic_ref").REWARD_NAMES):
+        assert (g(env._sums[k])[ids] == 0).all(), nm
+        np.testing.assert_array_equal(g(env._sums[k])[keep], S["episode_sums"][nm][keep], err_msg=nm)
     for k in ("root_states", "dof_pos", "dof_vel", "commands", "last_actions", "episode_length_buf"):
         np.testing.assert_allclose(g(getattr(env, k))[ids], R[k][ids], rtol=1e-6, atol=1e-6, err_msg=k)
         np.testing.assert_array_equal(g(getattr(env, k))[keep], S[k][keep], err_msg=k)
@@ -1489,6 +1602,63 @@ def test_episode_extras_ring_snapshots():
     assert any(not torch.equal(snaps[0], s) for s in snaps[1:])
 
 
+def test_episode_stats_across_steps():
+    """The episode statistics over consecutive launches (accumulators carried between launches and
+    cleared by the statistics block, the ring row each launch writes) at 77 envs, with an episode
+    length that is no multiple of dt (0.055 s: 6 steps; the means divide by 0.055, not 0.06).
+    Episode lengths are staggered so that the run has steps without a reset, and reset steps that
+    follow each other with different envs resetting: on a reset step the published means are those
+    of exactly that step's resetting envs, from the episode sums the step's post left (the GPU
+    snapshot before the post plus the oracle's increments of that post), to the bound of
+    _check_episode_stats; on any other step the statistics keep their values and EP_STATS[23] is 0.
+    Every published dict still holds its values at the end (the snapshot ring)."""
+    _need_gpu()
+    import pipeline_ref as PR
+    n = 77
+    env = _make_env(n, env__episode_length_s=0.055)
+    assert int(env._hgcfg.max_episode_length) == 6
+    cfg = _oracle_cfg(env)
+    names = __import__("envlogic_ref").REWARD_NAMES
+    g = lambda t: t.detach().cpu().numpy().copy()  # noqa: E731
+    _plant_episode_sums(env, 9)
+    env.episode_length_buf[:30] = 4       # time out at step 2, then step 9
+    env.episode_length_buf[30:60] = 5     # step 1, then step 8
+    env.episode_length_buf[76] = 5        # the last env (the partial K_post block)
+    gen = torch.Generator(device="cuda:0").manual_seed(31)
+    reset_sets, published = [], []
+    prev = g(env._ep_stats)
+    for t in range(12):
+        _step_only(env, torch.randn(n, 12, device="cuda:0", generator=gen) * 0.3, t)
+        S, hist_o, hist_p = snapshot(env)
+        before = {nm: S["episode_sums"][nm].copy() for nm in names}
+        extras = {}
+        _, _, _, reset, _, terms = PR.post(cfg, S, t + 1, hist_o, hist_p, extras=extras)
+        _post_once(env, t + 1)
+        env._publish_extras()
+        np.testing.assert_array_equal(g(env.reset_buf), reset)
+        rid = np.nonzero(reset)[0]
+        reset_sets.append(set(rid.tolist()))
+        stats = g(env._ep_stats)
+        if len(rid):
+            inc = _episode_scaled_terms(cfg, terms)
+            after = {nm: (before[nm] + inc[nm]).astype(np.float32) for nm in names}
+            _check_episode_stats(env, after, rid, extras["episode"], label=f"step {t}")
+        else:
+            np.testing.assert_array_equal(stats[:22], prev[:22])
+            assert stats[22] == 0 and stats[23] == 0
+            for name, v in env.extras["episode"].items():
+                assert float(v) == prev[names.index(name[4:])], (t, name)
+        published.append((env.extras["episode"], stats))
+        prev = stats
+    kinds = [bool(s) for s in reset_sets]
+    assert any(kinds) and not all(kinds), kinds
+    assert any(a and b and a != b for a, b in zip(reset_sets, reset_sets[1:])), reset_sets
+    assert any(76 in s for s in reset_sets)
+    for t, (d, stats) in enumerate(published):
+        for name, v in d.items():
+            assert float(v) == stats[names.index(name[4:])], (t, name)
+
+
 def test_runner_lazy_stats_are_last_iteration():
     """OnPolicyRunner.learn without a log writer reads each iteration's phase events and loss means
     one iteration late (no host wait at the iteration boundary); after learn() the stats are
@@ -1772,25 +1942,83 @@ def test_config1_workload_through_the_product():
         assert torch.isfinite(p).all()
 
 
-def test_wave_balancing_does_not_change_results(monkeypatch):
+def _order_bin(rows):
+    """hg_order_bin (csrc/hg_common.h): 12 bins, ceil(rows / 3) capped at 11, heaviest first."""
+    return 11 - np.minimum((np.maximum(rows, 0) + 2) // 3, 11)
+
+
+def _assert_env_order(n, order, rows):
+    """K_step's env order (HG_T_ENV_ORDER) against the rows it was sorted by (HG_T_ENV_ROWS), per
+    XCD range of csrc/hg_common.h: XCD x owns pairs p0 .. p0 + cnt - 1 of the nb = ceil(n / 2) env
+    pairs, i.e. envs e0 = 2 p0 .. e0 + m - 1; its slice of the order is a permutation of exactly
+    those envs, heaviest bin first (bin = 11 - min(ceil(rows / 3), 11), so non-decreasing), envs
+    of one bin in ascending id (a stable sort)."""
+    nb = (n + 1) // 2
+    covered = 0
+    for xcd in range(8):
+        cnt = (nb >> 3) + (1 if xcd < (nb & 7) else 0)
+        p0 = xcd * (nb >> 3) + min(xcd, nb & 7)
+        e0 = 2 * p0
+        m = max(0, min(n, 2 * (p0 + cnt)) - e0)
+        o = order[e0:e0 + m].astype(np.int64)
+        np.testing.assert_array_equal(np.sort(o), np.arange(e0, e0 + m), err_msg=f"XCD {xcd}: not a permutation")
+        bins = _order_bin(rows[o])
+        assert (np.diff(bins) >= 0).all(), (xcd, bins)
+        same = np.diff(bins) == 0
+        assert (np.diff(o)[same] > 0).all(), (xcd, o, bins)
+        covered += m
+    assert covered == n
+
+
+@pytest.mark.parametrize("n", [13, 77, 512, 1001, 4097])
+def test_wave_balancing_does_not_change_results(monkeypatch, n):
     """K_step's wave balancing (HG_WAVE_BALANCE, on by default: each XCD's envs re-paired by the
     previous step's constraint rows, heaviest wave and lightest on one SIMD) only changes which
-    env shares a wave: 30 policy steps of 512 envs (spawn, touchdown, contact) with and without it
-    give every physics field and the rewards bit for bit."""
+    env shares a wave: 30 policy steps (spawn, touchdown, contact) with and without it give every
+    physics field, the rewards and the dropped-row / non-finite counters bit for bit.  Env counts:
+    512 (even, equal XCD ranges); 13 (7 pairs, fewer than the 8 XCDs) and 77 (39 pairs: XCD
+    ranges of 5 and 4 pairs), odd, so the last wave runs an invalid half on env_order[n - 1]; 1001;
+    4097 (XCD 0 sorts 514 envs, 3 per thread with clamped thread ranges, the last XCD 511).  At 13
+    and 77 envs the run starts from the standing MJCF-friction state that drops 6 rows per substep
+    (test_row_budget_parity_standing_mjcf_friction) with the odd envs lifted 0.8 m (fewer rows:
+    another sort bin), so an env visited by two waves, or by none, shows in rows_dropped.  After
+    the balanced run the env order is checked against the rows it was sorted by
+    (_assert_env_order)."""
     _need_gpu()
-    from humanoid import _native as N
     outs = []
+    fields = ("root_states", "dof_pos", "dof_vel", "torques", "contact_forces", "rigid_state", "rew_buf",
+              "rows_dropped", "nonfinite_count")
     for flag in ("0", "1"):
         monkeypatch.setenv("HG_WAVE_BALANCE", flag)
-        env = _make_env(512)
         gen = torch.Generator(device="cuda:0").manual_seed(21)
-        for _ in range(30):
-            env.step(torch.randn(env.num_envs, 12, device="cuda:0", generator=gen) * 0.4)
+        if n < 100:
+            from humanoid.scripts import sim2sim as S2
+            env = S2.make_env("mjcf", n, 5.0)
+            for _ in range(80):
+                S2.step_direct(env, torch.zeros(n, 12, device="cuda:0"))
+            lo = torch.tensor([env._model.lower[b] for b in range(1, 13)], device="cuda:0")
+            env.dof_pos[:, [1, 7]] = lo[[1, 7]] - 0.01
+            env.root_states[1::2, 2] += 0.8  # odd envs in the air for the 30 steps: fewer rows, another sort bin
+            act = torch.zeros(n, 12, device="cuda:0")
+            act[:, [1, 7]] = (lo[[1, 7]] - 0.01) / env.cfg.control.action_scale
+            for _ in range(30):
+                S2.step_direct(env, act + torch.randn(n, 12, device="cuda:0", generator=gen) * 0.05)
+        else:
+            env = _make_env(n)
+            for _ in range(30):
+                env.step(torch.randn(env.num_envs, 12, device="cuda:0", generator=gen) * 0.4)
         torch.cuda.synchronize()
-        outs.append({k: getattr(env, k).detach().cpu().numpy().copy() for k in
-                     ("root_states", "dof_pos", "dof_vel", "torques", "contact_forces", "rigid_state", "rew_buf")})
+        outs.append({k: getattr(env, k).detach().cpu().numpy().copy() for k in fields})
+        if flag == "1":
+            order, rows = env.env_order.cpu().numpy(), env.env_rows.cpu().numpy()
+            _assert_env_order(n, order, rows)
+            assert len(np.unique(_order_bin(rows))) > 1, "one bin only: the sort was not exercised"
     for k in outs[0]:
         np.testing.assert_array_equal(outs[0][k], outs[1][k], err_msg=k)
+    if n < 100:
+        dropped = outs[0]["rows_dropped"]
+        print("rows dropped per env:", dropped)
+        assert (dropped[0::2] > 0).all(), dropped  # the standing envs, env n - 1 among them
 
 
 def test_learn_is_bitwise_reproducible():
