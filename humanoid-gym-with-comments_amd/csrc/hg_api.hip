@@ -13,7 +13,7 @@ extern "C" int hg_launch_step(const HgState* S, const hg_cfg* hcfg, const float*
                                hipStream_t stream);
 extern "C" int hg_launch_post(const HgState* S, const hg_cfg* hcfg, uint64_t counter, int mode, const uint8_t* mask,
                               float* frame_obs, float* frame_priv, HgWindow obs, HgWindow priv, float inv_len_s,
-                              int ep_slot, HgSink sink, hipStream_t stream);
+                              int ep_slot, HgSink sink, HgCurriculum cur, hipStream_t stream);
 
 namespace {
 
@@ -89,6 +89,9 @@ Layout make_layout(const hg_cfg* c) {
     if (id == HG_T_EP_STATS) { o += align256((48 + HG_EP_RING * 24) * sizeof(float)); continue; }
     if (id == HG_T_EP_STATS_RING) { L.off[id] = L.off[HG_T_EP_STATS] + 48 * sizeof(float); continue; }
     if (id == HG_T_ENV_ROWS || id == HG_T_ENV_ORDER) continue;  // views of the env_rows / env_order regions below
+    // CMD_RANGE_X region: the live range [2], then the latest mean terrain level [1]
+    if (id == HG_T_CMD_RANGE_X) { o += align256(3 * sizeof(float)); continue; }
+    if (id == HG_T_CURRICULUM_RING) { o += align256((size_t)HG_EP_RING * 2 * sizeof(float)); continue; }
     o += align256((size_t)soa_rows(id) * np * esize(dtype_of(id)));
   }
   // the observation histories: one sliding window per env row (hg_obs_window_frames)
@@ -123,6 +126,7 @@ struct Sim {
   uint64_t post_seq = 0;  // post/reset launches so far: EP_STATS ring row of the next one
   int ep_slot = 0;        // ring row written by the latest one
   HgSink sink{nullptr, nullptr, nullptr};  // one-shot: consumed by the next hg_post
+  int terrain_level_stat = 0;  // hg_publish_terrain_level
   std::string err;
 };
 
@@ -190,6 +194,8 @@ int hg_create(const hg_cfg* cfg, const hg_model* model, void* arena, size_t aren
     return fail(nullptr, HG_ERR_ARG, "heightfield terrain needs a device heightfield");
   if (cfg->curriculum && (!cfg->terrain_origins || cfg->terrain_rows < 1 || cfg->terrain_cols < 1))
     return fail(nullptr, HG_ERR_ARG, "terrain curriculum needs the device terrain_origins table");
+  if (cfg->cmd_curriculum && (cfg->max_episode_length <= 0 || !(cfg->cmd_max_curriculum >= 0.f)))
+    return fail(nullptr, HG_ERR_ARG, "command curriculum needs max_episode_length > 0 and cmd_max_curriculum >= 0");
   Sim* s = new Sim();
   s->cfg = *cfg;
   s->model = *model;
@@ -255,6 +261,7 @@ int hg_create(const hg_cfg* cfg, const hg_model* model, void* arena, size_t aren
   S.noise_counter = (uint64_t*)(s->arena + s->L.noise_counter);
   S.env_rows = (int32_t*)(s->arena + s->L.env_rows);
   S.env_order = (int32_t*)(s->arena + s->L.env_order);
+  S.cmd_range = (float*)P(HG_T_CMD_RANGE_X);
   {
     // K_step's wave balancing (hg_common.h hg_env_order_block, run by the post launch): on unless HG_WAVE_BALANCE=0
     const char* wb = getenv("HG_WAVE_BALANCE");
@@ -264,6 +271,7 @@ int hg_create(const hg_cfg* cfg, const hg_model* model, void* arena, size_t aren
   if (hipMemset(arena, 0, s->L.bytes) != hipSuccess ||
       hipMemcpy((void*)S.cfg, &s->cfg, sizeof(hg_cfg), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy((void*)S.model, &s->model, sizeof(hg_model), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(S.cmd_range, s->cfg.cmd_lin_x, 2 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemset(S.noise_counter, 0xFF, sizeof(uint64_t)) != hipSuccess) {
     delete s;
     return fail(nullptr, HG_ERR_HIP, "hip memset/memcpy failed (is the arena device memory?)");
@@ -306,6 +314,12 @@ int hg_tensor(void* sim, int id, hg_desc* d) {
       return HG_OK;
     case HG_T_EP_STATS_RING:
       d->ndim = 2; d->shape[0] = HG_EP_RING; d->shape[1] = 24; d->strides[0] = 24; d->strides[1] = 1;
+      return HG_OK;
+    case HG_T_CMD_RANGE_X:
+      d->ndim = 1; d->shape[0] = 2; d->strides[0] = 1;
+      return HG_OK;
+    case HG_T_CURRICULUM_RING:
+      d->ndim = 2; d->shape[0] = HG_EP_RING; d->shape[1] = 2; d->strides[0] = 2; d->strides[1] = 1;
       return HG_OK;
     case HG_T_CONTACT_FORCES:  // [N,13,3] (net_contact_force's shape), SoA storage
       d->ndim = 3; d->shape[0] = n; d->shape[1] = HG_NB; d->shape[2] = 3;
@@ -354,8 +368,15 @@ static int do_post(Sim* s, uint64_t counter, int mode, const uint8_t* mask, void
   // a step's post launch takes the pending rollout sink (reset launches leave it pending)
   const HgSink sink = mode == 0 ? s->sink : HgSink{nullptr, nullptr, nullptr};
   if (mode == 0) s->sink = HgSink{nullptr, nullptr, nullptr};
+  // command curriculum / curriculum extras: off (ring NULL) unless the cfg or the caller asks
+  HgCurriculum cur{nullptr, nullptr, 0};
+  if (s->cfg.cmd_curriculum || s->terrain_level_stat) {
+    cur.ring = (float*)(s->arena + s->L.off[HG_T_CURRICULUM_RING]) + 2 * slot;
+    cur.terrain_level = s->terrain_level_stat ? s->S.terrain_level : nullptr;
+    cur.update = s->cfg.cmd_curriculum && counter % (uint64_t)s->cfg.max_episode_length == 0;
+  }
   int rc = hg_launch_post(&s->S, &s->cfg, counter, mode, mask, (float*)(s->arena + s->L.frame_obs),
-                          (float*)(s->arena + s->L.frame_priv), wo, wp, inv_len_s, slot, sink, (hipStream_t)stream);
+                          (float*)(s->arena + s->L.frame_priv), wo, wp, inv_len_s, slot, sink, cur, (hipStream_t)stream);
   if (rc != 0) return fail(s, HG_ERR_HIP, "k_post launch failed");
   s->ep_slot = slot;
   s->post_seq++;
@@ -402,6 +423,8 @@ int hg_update_cfg(void* sim, const hg_cfg* cfg, void* stream) {
     return fail(s, HG_ERR_ARG, "hg_update_cfg: layout fields cannot change after hg_create");
   if (cfg->pgs_iterations < 0 || cfg->pgs_iterations > 1000 || !(cfg->sim_dt > 0.f))
     return fail(s, HG_ERR_ARG, "hg_update_cfg: bad solver parameters");
+  if (cfg->cmd_curriculum && (cfg->max_episode_length <= 0 || !(cfg->cmd_max_curriculum >= 0.f)))
+    return fail(s, HG_ERR_ARG, "hg_update_cfg: command curriculum needs max_episode_length > 0 and cmd_max_curriculum >= 0");
   s->cfg = *cfg;
   // the device copy is read by the env-logic launches, the host copy by K_step's launch (its
   // physics scalars go by value); the host source stays valid (it is the handle's)
@@ -416,7 +439,28 @@ int hg_reset_masked(void* sim, const uint8_t* mask, uint64_t counter, void* stre
   return do_post(s, counter, 1, mask, stream);
 }
 
+int hg_publish_terrain_level(void* sim, int on) {
+  Sim* s = (Sim*)sim;
+  if (!s) return HG_ERR_ARG;
+  s->terrain_level_stat = on != 0;
+  return HG_OK;
+}
+
 }  // extern "C"
+
+// ---- the live command range
+__global__ void k_set_cmd_range(float* range, float lo, float hi) {
+  range[0] = lo;
+  range[1] = hi;
+}
+
+extern "C" int hg_set_command_range_x(void* sim, float lo, float hi, void* stream) {
+  Sim* s = (Sim*)sim;
+  if (!s) return HG_ERR_ARG;
+  if (!(lo <= hi)) return fail(s, HG_ERR_ARG, "hg_set_command_range_x: need lo <= hi");
+  hipLaunchKernelGGL(k_set_cmd_range, dim3(1), dim3(1), 0, (hipStream_t)stream, s->S.cmd_range, lo, hi);
+  return hipGetLastError() == hipSuccess ? HG_OK : fail(s, HG_ERR_HIP, "k_set_cmd_range launch failed");
+}
 
 // ---- indexed state writes
 __global__ void k_set_dof(HgState S, const int32_t* ids, int n, const float* pos, const float* vel) {

@@ -10,6 +10,7 @@
 #define HG_NV 18
 #define HG_OBS1 47
 #define HG_PRIV1 73
+#define HG_REW_TRACKING_LIN_VEL 20  // index of tracking_lin_vel among the 22 reward terms (alphabetical)
 
 // ------------------------------------------------------------------------------------------------
 // arena: SoA per-env fields, each row padded to `np` elements (np = N rounded up to 64)
@@ -64,7 +65,31 @@ struct HgState {
   int balance;            // 1: K_step maps block -> env pair through env_order (hg_create: HG_WAVE_BALANCE)
   const hg_cfg* cfg;      // device copy
   const hg_model* model;  // device copy
+  float* cmd_range;       // [0..1] the live lin_vel_x command range (HG_T_CMD_RANGE_X, read when
+                          // cfg.cmd_curriculum), [2] the mean terrain level the latest resetting launch folded
 };
+
+// what the statistics block of the post launch needs for the command curriculum and the curriculum
+// extras (hg_envlogic.hip); ring == NULL: neither is on, the block does what it did without them
+struct HgCurriculum {
+  float* ring;                  // this launch's HG_T_CURRICULUM_RING row
+  const int32_t* terrain_level; // [n], NULL: no terrain-level mean (hg_publish_terrain_level off)
+  int update;                   // cfg.cmd_curriculum and counter % max_episode_length == 0
+};
+
+// update_command_curriculum (humanoid_env.py:1097-1106) on the finished accumulators of a post /
+// reset launch: tsum = sum of the resetting envs' tracking_lin_vel episode sums, cnt = how many
+// reset.  Widens (lo, hi) in place and returns true when the range moved.  reward_scale carries dt,
+// as the reference's reward_scales do after _prepare_reward_function.
+__device__ __forceinline__ bool hg_cmd_curriculum_rule(const hg_cfg* c, float tsum, float cnt, float& lo, float& hi) {
+  if (!(cnt > 0.f) || !(tsum / cnt / (float)c->max_episode_length > 0.8f * c->reward_scale[HG_REW_TRACKING_LIN_VEL])) return false;
+  const float m = c->cmd_max_curriculum;
+  const float nlo = fminf(fmaxf(lo - 0.5f, -m), 0.f), nhi = fminf(fmaxf(hi + 0.5f, 0.f), m);
+  const bool moved = nlo != lo || nhi != hi;
+  lo = nlo;
+  hi = nhi;
+  return moved;
+}
 
 // the rollout-storage slot a step's post launch also fills (hg_set_rollout_sink): rewards [n] f32,
 // dones [n] u8 and (optional) time-out flags [n] u8 — what hg_rollout_env writes with the value

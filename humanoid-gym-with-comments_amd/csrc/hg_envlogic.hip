@@ -60,7 +60,8 @@ __device__ Gait gait(const hg_cfg* cfg, int64_t ep) {
 __device__ void resample_commands(const hg_cfg* cfg, HgState& S, int e, uint64_t step, uint32_t salt) {
   const int np = S.np;
   u4 r = rng4(cfg, e, step, salt, RNG_CMD);
-  float cx = (cfg->cmd_lin_x[1] - cfg->cmd_lin_x[0]) * u01(r.x) + cfg->cmd_lin_x[0];
+  const float* lx = cfg->cmd_curriculum ? S.cmd_range : cfg->cmd_lin_x;  // the live range under the command curriculum
+  float cx = (lx[1] - lx[0]) * u01(r.x) + lx[0];
   float cy = (cfg->cmd_lin_y[1] - cfg->cmd_lin_y[0]) * u01(r.y) + cfg->cmd_lin_y[0];
   S.commands[0 * np + e] = cx;
   S.commands[1 * np + e] = cy;
@@ -500,6 +501,11 @@ __device__ __forceinline__ float dist_term(float dx, float dy, float lo, float h
 }
 }  // namespace
 
+// CURR: cfg.cmd_curriculum, as a template parameter so that the default instantiation reads the
+// lin_vel_x bounds from the kernel arguments exactly as it did before the command curriculum (a
+// run-time select between the two sources became a select of pointers and a vector load of the
+// kernel-argument segment at the top of every wave: ≈ 1 µs per launch)
+template <bool CURR>
 __global__ void __launch_bounds__(64 * PWAVES) k_post_step(HgState S, const hg_cfg C, uint64_t counter,
                                                               float* __restrict__ frame_obs, float* __restrict__ frame_priv) {
   __shared__ float xs[X_NSLOT * PEB];
@@ -522,6 +528,10 @@ __global__ void __launch_bounds__(64 * PWAVES) k_post_step(HgState S, const hg_c
 #define X(slot) xs[(slot) * PEB + l]
   const int f0 = C.feet_body[0], f1 = C.feet_body[1];
   const int k0 = C.knee_body[0], k1 = C.knee_body[1];
+  // lin_vel_x bounds of both command draws: the live range under the command curriculum (no block of
+  // this launch writes it; k_window_stats' statistics block does, after k_cmd_curriculum)
+  float lin_x0 = C.cmd_lin_x[0], lin_x1 = C.cmd_lin_x[1];
+  if (CURR) { lin_x0 = S.cmd_range[0]; lin_x1 = S.cmd_range[1]; }
 
   // ---------------- L: staging loads
   {
@@ -668,7 +678,7 @@ __global__ void __launch_bounds__(64 * PWAVES) k_post_step(HgState S, const hg_c
         float cmd[4] = {X(X_CMD), X(X_CMD + 1), X(X_CMD + 2), X(X_CMD + 3)};
         if ((int)ep % C.resample_interval == 0) {
           u4 r = rng4(cfg, e, counter, 0, RNG_CMD);
-          float cx = (C.cmd_lin_x[1] - C.cmd_lin_x[0]) * u01(r.x) + C.cmd_lin_x[0];
+          float cx = (lin_x1 - lin_x0) * u01(r.x) + lin_x0;
           float cy = (C.cmd_lin_y[1] - C.cmd_lin_y[0]) * u01(r.y) + C.cmd_lin_y[0];
           if (C.heading_command) cmd[3] = (C.cmd_heading[1] - C.cmd_heading[0]) * u01(r.z) + C.cmd_heading[0];
           else cmd[2] = (C.cmd_ang_yaw[1] - C.cmd_ang_yaw[0]) * u01(r.z) + C.cmd_ang_yaw[0];
@@ -988,7 +998,7 @@ __global__ void __launch_bounds__(64 * PWAVES) k_post_step(HgState S, const hg_c
         case 5: {  // _resample_commands (salt 1); the step's heading command stays in slot 2 or 3
           const u4 r = rng4(cfg, e, counter, 1, RNG_CMD);
           float cmd[4] = {0.f, 0.f, X(X_CMD2 + 2), X(X_CMD2 + 3)};
-          const float cx = (C.cmd_lin_x[1] - C.cmd_lin_x[0]) * u01(r.x) + C.cmd_lin_x[0];
+          const float cx = (lin_x1 - lin_x0) * u01(r.x) + lin_x0;
           const float cy = (C.cmd_lin_y[1] - C.cmd_lin_y[0]) * u01(r.y) + C.cmd_lin_y[0];
           if (C.heading_command) cmd[3] = (C.cmd_heading[1] - C.cmd_heading[0]) * u01(r.z) + C.cmd_heading[0];
           else cmd[2] = (C.cmd_ang_yaw[1] - C.cmd_ang_yaw[0]) * u01(r.z) + C.cmd_ang_yaw[0];
@@ -1120,11 +1130,50 @@ __global__ void __launch_bounds__(64 * PWAVES) k_post_step(HgState S, const hg_c
 #undef X
 }
 
+// Command curriculum (update_command_curriculum + the order of reset_idx, humanoid_env.py:1097-1106,
+// 1120-1129): the reference widens command_ranges["lin_vel_x"] BEFORE the same reset_idx draws the
+// resetting envs' commands.  The decision needs the sums of all resetting envs, which only exist
+// once every block of k_post_step / k_post has run, so it is a launch of its own between that
+// kernel and k_window_stats — on the launches whose counter is a multiple of max_episode_length
+// only (the host knows that from the counter).  Every lane evaluates the rule on the finished
+// accumulators (read-only here; the statistics block of k_window_stats repeats the decision, writes
+// the new range and clears the accumulators, so no block reads a range another block of its launch
+// writes).  If the range moved, the lane of a resetting env redraws that env's reset command from
+// the same Philox key with the new x bounds (the 0.2 norm gate multiplies x and y, so both) and
+// patches commands[0..1] and the command columns 2, 3 of the env's newest frames, which
+// k_window_stats then stacks.  One lane per env.
+__global__ void __launch_bounds__(256) k_cmd_curriculum(HgState S, uint64_t counter, float* __restrict__ frame_obs,
+                                                         float* __restrict__ frame_priv) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= S.n) return;
+  const hg_cfg* cfg = S.cfg;
+  const float* acc = S.ep_stats + 24;
+  float lo = S.cmd_range[0], hi = S.cmd_range[1];
+  if (!hg_cmd_curriculum_rule(cfg, acc[HG_REW_TRACKING_LIN_VEL], acc[22], lo, hi)) return;
+  if (!S.reset_buf[e]) return;
+  const int np = S.np;
+  const u4 r = rng4(cfg, e, counter, 1, RNG_CMD);
+  const float cx = (hi - lo) * u01(r.x) + lo;
+  const float cy = (cfg->cmd_lin_y[1] - cfg->cmd_lin_y[0]) * u01(r.y) + cfg->cmd_lin_y[0];
+  const float keep = sqrtf(cx * cx + cy * cy) > 0.2f ? 1.f : 0.f;
+  const float c0 = cx * keep, c1 = cy * keep;
+  S.commands[0 * np + e] = c0;
+  S.commands[1 * np + e] = c1;
+  const float clip = cfg->clip_observations;
+  const float o0 = fminf(fmaxf(c0 * cfg->obs_lin_vel, -clip), clip), o1 = fminf(fmaxf(c1 * cfg->obs_lin_vel, -clip), clip);
+  float* O = frame_obs + (size_t)e * HG_OBS1;
+  float* P = frame_priv + (size_t)e * HG_PRIV1;
+  O[2] = o0; O[3] = o1;
+  P[2] = o0; P[3] = o1;
+}
+
 // history windows (HgWindow, hg_api.hip): the reference's deque append + stack
 // (humanoid_env.py:880-887, history zeroed on reset) as one frame write per (env, table) into the
 // row's sliding window instead of a copy of the whole stack; one block per (env, table) row.  The
 // last block also folds the episode statistics (ep_stats[k] = acc[k] / n_reset / episode_length_s
-// when any env reset) and clears the accumulators.
+// when any env reset) and clears the accumulators; with the command curriculum or the terrain-level
+// extra on (HgCurriculum) it also writes the widened lin_vel_x range and the launch's
+// (max_command_x, mean terrain level) ring row.
 constexpr int WIN_ROWS = 4;  // (env, table) rows per k_window_stats block, one wave each
 __global__ void __launch_bounds__(64 * WIN_ROWS) k_window_stats(HgWindow A, HgWindow B, const float* __restrict__ frame_a,
                                                       const float* __restrict__ frame_b,
@@ -1133,7 +1182,9 @@ __global__ void __launch_bounds__(64 * WIN_ROWS) k_window_stats(HgWindow A, HgWi
                                                       const int32_t* __restrict__ env_rows,
                                                       int32_t* __restrict__ env_order, int nsort, HgSink sink,
                                                       const float* __restrict__ rew,
-                                                      const uint8_t* __restrict__ time_out, int nsink) {
+                                                      const uint8_t* __restrict__ time_out, int nsink,
+                                                      const hg_cfg* __restrict__ cfg, float* __restrict__ cmd_range,
+                                                      HgCurriculum cur) {
   static_assert(64 * WIN_ROWS == HG_ORD_T, "the order blocks use the window block's threads");
   // blocks 0 .. nsort - 1: the next K_step's env order (hg_common.h), first so that they start
   // with the launch and run beside the window rows
@@ -1156,6 +1207,37 @@ __global__ void __launch_bounds__(64 * WIN_ROWS) k_window_stats(HgWindow A, HgWi
     const int k = threadIdx.x;
     float* acc = ep_stats + 24;
     const float cnt = acc[22];
+    if (cur.ring) {  // block-uniform
+      // extras["episode"]["terrain_level"] = mean(terrain_levels.float()) over ALL envs, as they stand
+      // after this launch's resets (humanoid_env.py:1146-1147): an integer sum (exact, order-free)
+      // folded to sum / n; kept from the previous resetting launch when no env reset
+      float tmean = 0.f;
+      const bool fold = cur.terrain_level && cnt > 0.f;  // block-uniform
+      if (fold) {
+        __shared__ int tl_part[64 * WIN_ROWS];
+        int part = 0;
+        for (int i = k; i < n; i += 64 * WIN_ROWS) part += cur.terrain_level[i];
+        tl_part[k] = part;
+        __syncthreads();
+        for (int s2 = 32 * WIN_ROWS; s2 > 0; s2 >>= 1) {
+          if (k < s2) tl_part[k] += tl_part[k + s2];
+          __syncthreads();
+        }
+        tmean = (float)tl_part[0] / (float)n;
+      }
+      if (k == 0) {
+        // the decision k_cmd_curriculum took on the same accumulators: the range it drew with
+        if (!fold) tmean = cmd_range[2];
+        float lo = cmd_range[0], hi = cmd_range[1];
+        if (cur.update && hg_cmd_curriculum_rule(cfg, acc[HG_REW_TRACKING_LIN_VEL], cnt, lo, hi)) {
+          cmd_range[0] = lo;
+          cmd_range[1] = hi;
+        }
+        cmd_range[2] = tmean;
+        cur.ring[0] = hi;  // extras["episode"]["max_command_x"] (:1148-1149)
+        cur.ring[1] = tmean;
+      }
+    }
     __syncthreads();
     float v = k < 24 ? ep_stats[k] : 0.f;
     if (k < HG_NUM_REWARDS && cnt > 0.f) v = acc[k] / cnt * inv_len_s;
@@ -1192,14 +1274,21 @@ __global__ void __launch_bounds__(64 * WIN_ROWS) k_window_stats(HgWindow A, HgWi
 
 extern "C" int hg_launch_post(const HgState* S, const hg_cfg* hcfg, uint64_t counter, int mode, const uint8_t* mask,
                               float* frame_obs, float* frame_priv, HgWindow obs, HgWindow priv, float inv_len_s,
-                              int ep_slot, HgSink sink, hipStream_t stream) {
+                              int ep_slot, HgSink sink, HgCurriculum cur, hipStream_t stream) {
   const int n = S->n;
-  if (mode == 0)
-    hipLaunchKernelGGL(k_post_step, dim3((n + PEB - 1) / PEB), dim3(64 * PWAVES), 0, stream, *S, *hcfg, counter,
+  if (mode == 0 && hcfg->cmd_curriculum)
+    hipLaunchKernelGGL(k_post_step<true>, dim3((n + PEB - 1) / PEB), dim3(64 * PWAVES), 0, stream, *S, *hcfg, counter,
+                       frame_obs, frame_priv);
+  else if (mode == 0)
+    hipLaunchKernelGGL(k_post_step<false>, dim3((n + PEB - 1) / PEB), dim3(64 * PWAVES), 0, stream, *S, *hcfg, counter,
                        frame_obs, frame_priv);
   else
     hipLaunchKernelGGL(k_post, dim3((n + 63) / 64), dim3(64), 0, stream, *S, counter, mode, mask, frame_obs,
                        frame_priv);
+  // reset_idx widens the command range before it draws (humanoid_env.py:1120-1129): on a curriculum
+  // launch the resetting envs' commands are redrawn if the range moved
+  if (cur.update)
+    hipLaunchKernelGGL(k_cmd_curriculum, dim3((n + 255) / 256), dim3(256), 0, stream, *S, counter, frame_obs, frame_priv);
   // the env-order blocks (K_step's wave balancing), WIN_ROWS (env, table) rows per block, the
   // statistics block
   const int nsort = S->balance ? 8 : 0;
@@ -1207,6 +1296,6 @@ extern "C" int hg_launch_post(const HgState* S, const hg_cfg* hcfg, uint64_t cou
   const int g = nsort + nsink + (2 * n + WIN_ROWS - 1) / WIN_ROWS + 1;
   hipLaunchKernelGGL(k_window_stats, dim3(g), dim3(64 * WIN_ROWS), 0, stream, obs, priv, frame_obs, frame_priv,
                      S->reset_buf, n, S->ep_stats, inv_len_s, ep_slot, S->env_rows, S->env_order, nsort, sink, S->rew,
-                     S->time_out, nsink);
+                     S->time_out, nsink, S->cfg, S->cmd_range, cur);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }

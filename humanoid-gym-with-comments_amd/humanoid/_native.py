@@ -74,6 +74,7 @@ class HgCfg(ctypes.Structure):
         ("seed", ctypes.c_uint64),
         ("curriculum", i32), ("terrain_rows", i32), ("terrain_cols", i32), ("terrain_env_length", f32),
         ("max_episode_length_s", f32), ("env_offset", i32), ("terrain_origins", ctypes.c_void_p),
+        ("cmd_curriculum", i32), ("cmd_max_curriculum", f32),
     ]
 
 
@@ -90,14 +91,15 @@ TENSOR_IDS = [
     "FEET_AIR_TIME", "LAST_CONTACTS", "FEET_HEIGHT", "LAST_FEET_Z", "ENV_FRICTION", "BODY_MASS",
     "PUSH_FORCE", "PUSH_TORQUE", "BASE_LIN_VEL", "BASE_ANG_VEL", "PROJ_GRAVITY", "BASE_EULER",
     "REF_DOF_POS", "ENV_ORIGINS", "EP_STATS", "CONTACT_LAMBDA", "NONFINITE", "TERRAIN_LEVEL", "TERRAIN_TYPE",
-    "EP_STATS_RING", "ROWS_DROPPED", "ENV_ROWS", "ENV_ORDER",
+    "EP_STATS_RING", "ROWS_DROPPED", "ENV_ROWS", "ENV_ORDER", "CMD_RANGE_X", "CURRICULUM_RING",
 ]
 EP_RING = 64  # HG_EP_RING
 T = {name: i for i, name in enumerate(TENSOR_IDS)}
 
 # every symbol include/hgsim.h declares (checked by tests/test_boundary.py)
 EXPORTS = ["hg_arena_bytes", "hg_create", "hg_destroy", "hg_last_error", "hg_tensor", "hg_step",
-           "hg_post", "hg_set_rollout_sink", "hg_ep_stats_slot", "hg_obs_head", "hg_obs_window_advance", "hg_update_cfg", "hg_reset_masked", "hg_set_dof_state_indexed", "hg_set_root_state_indexed",
+           "hg_post", "hg_set_rollout_sink", "hg_ep_stats_slot", "hg_obs_head", "hg_obs_window_advance", "hg_update_cfg", "hg_reset_masked",
+           "hg_set_command_range_x", "hg_publish_terrain_level", "hg_set_dof_state_indexed", "hg_set_root_state_indexed",
            "hg_set_root_state", "hg_set_env_props",
            "hg_measure_heights", "hg_gae_scan", "hg_gae_stats_len", "hg_gae_normalize", "hg_adam_step", "hg_adam_chunk", "hg_kl_mean", "hg_kl_lr_rule",
            "hg_rollout_act", "hg_rollout_act_head", "hg_rollout_act_tail", "hg_rollout_env", "hg_gather_rows", "hg_gather_rows_ex", "hg_gather_stacked", "hg_ppo_loss", "hg_ppo_loss_lr", "hg_ppo_loss_scratch", "hg_ppo_loss_backward",
@@ -176,6 +178,10 @@ def load_library(path=LIB_PATH):
     L.hg_update_cfg.argtypes = [vp, ctypes.POINTER(HgCfg), vp]
     L.hg_reset_masked.restype = ctypes.c_int
     L.hg_reset_masked.argtypes = [vp, vp, ctypes.c_uint64, vp]
+    L.hg_set_command_range_x.restype = ctypes.c_int
+    L.hg_set_command_range_x.argtypes = [vp, ctypes.c_float, ctypes.c_float, vp]
+    L.hg_publish_terrain_level.restype = ctypes.c_int
+    L.hg_publish_terrain_level.argtypes = [vp, ctypes.c_int]
     L.hg_set_dof_state_indexed.restype = ctypes.c_int
     L.hg_set_dof_state_indexed.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp]
     L.hg_set_root_state_indexed.restype = ctypes.c_int

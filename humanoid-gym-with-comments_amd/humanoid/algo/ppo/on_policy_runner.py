@@ -275,9 +275,13 @@ class OnPolicyRunner:
 
     def save(self, path, infos=None):
         os.makedirs(os.path.dirname(path), exist_ok=True)
-        torch.save({"model_state_dict": self.alg.actor_critic.state_dict(),
-                    "optimizer_state_dict": self.alg.optimizer.state_dict(),
-                    "iter": self.current_learning_iteration, "infos": infos}, path)
+        d = {"model_state_dict": self.alg.actor_critic.state_dict(),
+             "optimizer_state_dict": self.alg.optimizer.state_dict(),
+             "iter": self.current_learning_iteration, "infos": infos}
+        if hasattr(self.env, "refresh_command_ranges"):
+            # the command curriculum's lin_vel_x range (the reference loses it on resume)
+            d["command_range_x"] = [float(v) for v in self.env.refresh_command_ranges()]
+        torch.save(d, path)
 
     def load(self, path, load_optimizer=True):
         d = torch.load(path, map_location=self.device, weights_only=True)
@@ -285,6 +289,8 @@ class OnPolicyRunner:
         if load_optimizer:
             self.alg.optimizer.load_state_dict(d["optimizer_state_dict"])
         self.current_learning_iteration = d["iter"]
+        if d.get("command_range_x") is not None and hasattr(self.env, "set_command_range_x"):
+            self.env.set_command_range_x(*d["command_range_x"])
         return d["infos"]
 
     def get_inference_policy(self, device=None):

@@ -128,6 +128,9 @@ def build_hg_cfg(cfg, num_envs, sim_dt, seed, model_js, heightfield=None, hf_sha
         c.curriculum = 1
         c.terrain_rows, c.terrain_cols = terrain_shape
         c.terrain_origins = terrain_origins
+    # command curriculum (update_command_curriculum, humanoid_env.py:1097-1106)
+    c.cmd_curriculum = int(bool(getattr(cfg.commands, "curriculum", False)))
+    c.cmd_max_curriculum = float(getattr(cfg.commands, "max_curriculum", 0.0))
     aux = dict(feet=feet, knees=knees, dof_names=dofs, body_names=bodies, kp=kp, kd=kd, torque_limits=tl,
                default_dof_pos=dd, limits=limits, velocity=velocity, scales=scales)
     return c, aux
@@ -243,6 +246,9 @@ class XBotLFreeEnv(BaseTask):
                                   ctypes.c_void_p(self._arena_base.data_ptr()), ctypes.c_size_t(nbytes),
                                   ctypes.byref(handle)))
         self.sim = handle
+        if mesh == "trimesh":
+            # extras["episode"]["terrain_level"] (humanoid_env.py:1146-1147): the post launches fold the mean level
+            N.check(self.hg.hg_publish_terrain_level(self.sim, 1), self.sim)
         self.num_dof = self.num_dofs = 12
         self.num_bodies = len(self._aux["body_names"])
         self.dof_names = self._aux["dof_names"]
@@ -311,6 +317,10 @@ class XBotLFreeEnv(BaseTask):
         self.env_origins = self._view(T["ENV_ORIGINS"])
         self._ep_stats = self._view(T["EP_STATS"])
         self._ep_ring = self._view(T["EP_STATS_RING"])
+        # the live lin_vel_x command range (commands.curriculum) and the per-launch snapshots of
+        # (max_command_x, mean terrain level), rows as _ep_ring's
+        self._cmd_range = self._view(T["CMD_RANGE_X"])
+        self._curriculum_ring = self._view(T["CURRICULUM_RING"])
         self.nonfinite_count = self._view(T["NONFINITE"])
         # constraint rows / contact points the solver's row budget dropped, per env, summed over
         # substeps (diagnostic; 0 in normal operation)
@@ -483,6 +493,11 @@ class XBotLFreeEnv(BaseTask):
         if views is None:
             stats = self._ep_ring[slot]
             views = cache[slot] = {"rew_" + n: stats[REWARD_NAMES.index(n)] for n in self.reward_names}
+            # the curriculum extras under the reference's own conditions (humanoid_env.py:1146-1149)
+            if self.cfg.terrain.mesh_type == "trimesh":
+                views["terrain_level"] = self._curriculum_ring[slot, 1]
+            if self.cfg.commands.curriculum:
+                views["max_command_x"] = self._curriculum_ring[slot, 0]
         self.extras = {"episode": dict(views), "time_outs": self.time_out_buf}
 
     def update_push_curriculum(self, iteration):
@@ -500,6 +515,19 @@ class XBotLFreeEnv(BaseTask):
             self._hgcfg.max_push_ang_vel = vang
             N.check(self.hg.hg_update_cfg(self.sim, ctypes.byref(self._hgcfg), self._stream()), self.sim)
         self.push_scale = (float(self._hgcfg.max_push_vel_xy), float(self._hgcfg.max_push_ang_vel))
+
+    def refresh_command_ranges(self):
+        """Read the live lin_vel_x range (widened on the device by the command curriculum,
+        humanoid_env.py:1097-1106) back into command_ranges["lin_vel_x"]: one host read, so nothing
+        on the step path calls it.  Returns [lo, hi]."""
+        lo, hi = self._cmd_range.tolist()
+        self.command_ranges["lin_vel_x"] = [lo, hi]
+        return [lo, hi]
+
+    def set_command_range_x(self, lo, hi):
+        """Set the live lin_vel_x range (checkpoint resume), ordered on the current stream."""
+        N.check(self.hg.hg_set_command_range_x(self.sim, float(lo), float(hi), self._stream()), self.sim)
+        self.command_ranges["lin_vel_x"] = [float(lo), float(hi)]
 
     def _launch_reset(self, mask_u8):
         mp = ctypes.c_void_p(mask_u8.data_ptr()) if mask_u8 is not None else None

@@ -140,6 +140,14 @@ typedef struct hg_cfg {
   int32_t env_offset;                   /* global id of this shard's env 0 (data parallel): every Philox
                                          * draw is keyed by the global env id */
   const float* terrain_origins;         /* device [rows, cols, 3], caller-owned */
+  /* command curriculum (update_command_curriculum, humanoid_env.py:1097-1106; commands.curriculum /
+   * max_curriculum, humanoid_config.py): when cmd_curriculum != 0 the lin_vel_x bounds of every
+   * command draw are the live range HG_T_CMD_RANGE_X (initialised from cmd_lin_x), which post / reset
+   * launches whose counter is a multiple of max_episode_length widen by 0.5 on both sides, up to
+   * +- cmd_max_curriculum, when the resetting envs' mean tracking_lin_vel episode sum is above 80 % of
+   * its maximum — before those envs' commands are drawn.  0: cmd_lin_x is used as is. */
+  int32_t cmd_curriculum;
+  float cmd_max_curriculum;
 } hg_cfg;
 
 typedef struct hg_desc {
@@ -189,6 +197,11 @@ enum hg_tensor_id {
                             wave-balancing sort key) */
   HG_T_ENV_ORDER,        /* [N] int32, read-only diagnostic: the env K_step's half-wave k runs, as the latest post
                             launch sorted it (a permutation of each XCD's env range; identity without balancing) */
+  HG_T_CMD_RANGE_X,      /* [2] f32: the live lin_vel_x command range (command_ranges["lin_vel_x"]); hg_create sets it
+                            to cfg.cmd_lin_x, hg_update_cfg leaves it alone, hg_set_command_range_x writes it */
+  HG_T_CURRICULUM_RING,  /* [HG_EP_RING, 2] f32: (max_command_x, mean terrain level) as each post/reset launch left
+                            them, launch k in row k % HG_EP_RING (hg_ep_stats_slot), the ring discipline of
+                            HG_T_EP_STATS_RING; written when cfg.cmd_curriculum != 0 or hg_publish_terrain_level is on */
   HG_T_COUNT
 };
 
@@ -235,6 +248,16 @@ int hg_obs_window_advance(void* sim);
 int hg_update_cfg(void* sim, const hg_cfg* cfg, void* stream);
 /* replaces reset_idx() (humanoid_env.py:1109-1163) for an explicit device mask [N] (u8). */
 int hg_reset_masked(void* sim, const uint8_t* mask, uint64_t counter, void* stream);
+/* Stream-ordered write of the live lin_vel_x command range HG_T_CMD_RANGE_X (the assignment to
+ * command_ranges["lin_vel_x"] of update_command_curriculum, humanoid_env.py:1097-1106, done from
+ * outside): restores the range a checkpoint stored.  lo <= hi.  The curriculum ring rows keep
+ * what the latest launch wrote until the next post / reset launch. */
+int hg_set_command_range_x(void* sim, float lo, float hi, void* stream);
+/* on != 0: every later post / reset launch in which some env resets also folds
+ * mean(terrain_levels.float()) over all envs (extras["episode"]["terrain_level"], humanoid_env.py:
+ * 1146-1147) into column 1 of its HG_T_CURRICULUM_RING row (carried forward when no env resets);
+ * exact for num_envs * max level < 2^24.  Host-side bookkeeping, off at hg_create. */
+int hg_publish_terrain_level(void* sim, int on);
 
 /* ---- indexed state writes (replace set_*_tensor_indexed, humanoid_env.py:1046-1048,1070-1072,680-681) ---- */
 /* env_ids: device int32 [n]; dof_pos/dof_vel: device [n,D]; root: device [n,13] */
