@@ -10,10 +10,12 @@
 #include "hg_common.h"
 
 extern "C" int hg_launch_step(const HgState* S, const hg_cfg* hcfg, const float* actions, uint64_t step_counter,
-                               hipStream_t stream);
+                               int per_env_actuators, hipStream_t stream);
 extern "C" int hg_launch_post(const HgState* S, const hg_cfg* hcfg, uint64_t counter, int mode, const uint8_t* mask,
                               float* frame_obs, float* frame_priv, HgWindow obs, HgWindow priv, float inv_len_s,
                               int ep_slot, HgSink sink, HgCurriculum cur, hipStream_t stream);
+extern "C" int hg_launch_actuator_draw(const HgState* S, uint64_t counter, int mode, const uint8_t* mask,
+                                       hipStream_t stream);
 
 namespace {
 
@@ -43,7 +45,8 @@ int soa_rows(int id) {
   switch (id) {
     case HG_T_ROOT_STATE: return 13;
     case HG_T_DOF_POS: case HG_T_DOF_VEL: case HG_T_TORQUES: case HG_T_ACTIONS: case HG_T_LAST_ACTIONS:
-    case HG_T_LAST_LAST_ACTIONS: case HG_T_LAST_DOF_VEL: case HG_T_REF_DOF_POS: return HG_ND;
+    case HG_T_LAST_LAST_ACTIONS: case HG_T_LAST_DOF_VEL: case HG_T_REF_DOF_POS: case HG_T_KP_SCALE:
+    case HG_T_KD_SCALE: case HG_T_ARMATURE_ADD: return HG_ND;
     case HG_T_CONTACT_FORCES: return HG_NB * 3;
     case HG_T_RIGID_STATE: return HG_NB * 13;
     case HG_T_LAST_ROOT_VEL: return 6;
@@ -127,12 +130,26 @@ struct Sim {
   int ep_slot = 0;        // ring row written by the latest one
   HgSink sink{nullptr, nullptr, nullptr};  // one-shot: consumed by the next hg_post
   int terrain_level_stat = 0;  // hg_publish_terrain_level
+  int actuator_props = 0;      // hg_set_actuator_props was called: K_step reads the per-env actuator regions
   std::string err;
 };
 
 int fail(Sim* s, int code, const std::string& m) {
   if (s) s->err = m; else g_create_error = m;
   return code;
+}
+
+// hg_cfg.actuator_rand: the four draw ranges (checked only when the option is on, so a zeroed
+// struct with the option off stays valid)
+const char* actuator_cfg_error(const hg_cfg* c) {
+  if (!c->actuator_rand) return nullptr;
+  const float* r[4] = {c->act_kp_range, c->act_kd_range, c->act_strength_range, c->act_armature_range};
+  for (int k = 0; k < 4; k++)
+    if (!(r[k][0] <= r[k][1])) return "actuator randomisation needs lo <= hi in every range";
+  for (int k = 0; k < 3; k++)
+    if (!(r[k][0] > 0.f)) return "actuator randomisation needs kp / kd / strength scale bounds > 0";
+  if (!(r[3][0] >= 0.f)) return "actuator randomisation needs armature bounds >= 0";
+  return nullptr;
 }
 
 __global__ void k_init(HgState S) {
@@ -154,6 +171,10 @@ __global__ void k_init(HgState S) {
   S.proj_gravity[2 * np + e] = -1.0f;
   S.reset_buf[e] = 1;
   S.env_order[e] = e;  // identity until the first step has counted rows
+  for (int j = 0; j < HG_ND; j++) {  // the shared actuator model (armature_add stays 0)
+    S.kp_scale[j * np + e] = 1.0f;
+    S.kd_scale[j * np + e] = 1.0f;
+  }
 }
 
 }  // namespace
@@ -196,6 +217,7 @@ int hg_create(const hg_cfg* cfg, const hg_model* model, void* arena, size_t aren
     return fail(nullptr, HG_ERR_ARG, "terrain curriculum needs the device terrain_origins table");
   if (cfg->cmd_curriculum && (cfg->max_episode_length <= 0 || !(cfg->cmd_max_curriculum >= 0.f)))
     return fail(nullptr, HG_ERR_ARG, "command curriculum needs max_episode_length > 0 and cmd_max_curriculum >= 0");
+  if (const char* m = actuator_cfg_error(cfg)) return fail(nullptr, HG_ERR_ARG, m);
   Sim* s = new Sim();
   s->cfg = *cfg;
   s->model = *model;
@@ -262,6 +284,9 @@ int hg_create(const hg_cfg* cfg, const hg_model* model, void* arena, size_t aren
   S.env_rows = (int32_t*)(s->arena + s->L.env_rows);
   S.env_order = (int32_t*)(s->arena + s->L.env_order);
   S.cmd_range = (float*)P(HG_T_CMD_RANGE_X);
+  S.kp_scale = (float*)P(HG_T_KP_SCALE);
+  S.kd_scale = (float*)P(HG_T_KD_SCALE);
+  S.armature_add = (float*)P(HG_T_ARMATURE_ADD);
   {
     // K_step's wave balancing (hg_common.h hg_env_order_block, run by the post launch): on unless HG_WAVE_BALANCE=0
     const char* wb = getenv("HG_WAVE_BALANCE");
@@ -344,7 +369,8 @@ int hg_tensor(void* sim, int id, hg_desc* d) {
 int hg_step(void* sim, const float* actions, uint64_t step_counter, void* stream) {
   Sim* s = (Sim*)sim;
   if (!s || !actions) return fail(s, HG_ERR_ARG, "null argument");
-  const int rc = hg_launch_step(&s->S, &s->cfg, actions, step_counter, (hipStream_t)stream);
+  const int rc = hg_launch_step(&s->S, &s->cfg, actions, step_counter, s->cfg.actuator_rand != 0 || s->actuator_props,
+                                (hipStream_t)stream);
   if (rc != 0) return fail(s, HG_ERR_HIP, "k_step launch failed");
   return HG_OK;
 }
@@ -378,6 +404,10 @@ static int do_post(Sim* s, uint64_t counter, int mode, const uint8_t* mask, void
   int rc = hg_launch_post(&s->S, &s->cfg, counter, mode, mask, (float*)(s->arena + s->L.frame_obs),
                           (float*)(s->arena + s->L.frame_priv), wo, wp, inv_len_s, slot, sink, cur, (hipStream_t)stream);
   if (rc != 0) return fail(s, HG_ERR_HIP, "k_post launch failed");
+  // actuator randomisation: the envs this launch reset get new rows (after the post kernels, so
+  // nothing is inserted into them; the default configuration launches nothing)
+  if (s->cfg.actuator_rand && hg_launch_actuator_draw(&s->S, counter, mode, mask, (hipStream_t)stream) != 0)
+    return fail(s, HG_ERR_HIP, "k_actuator_draw launch failed");
   s->ep_slot = slot;
   s->post_seq++;
   s->head = head;
@@ -425,6 +455,7 @@ int hg_update_cfg(void* sim, const hg_cfg* cfg, void* stream) {
     return fail(s, HG_ERR_ARG, "hg_update_cfg: bad solver parameters");
   if (cfg->cmd_curriculum && (cfg->max_episode_length <= 0 || !(cfg->cmd_max_curriculum >= 0.f)))
     return fail(s, HG_ERR_ARG, "hg_update_cfg: command curriculum needs max_episode_length > 0 and cmd_max_curriculum >= 0");
+  if (const char* m = actuator_cfg_error(cfg)) return fail(s, HG_ERR_ARG, std::string("hg_update_cfg: ") + m);
   s->cfg = *cfg;
   // the device copy is read by the env-logic launches, the host copy by K_step's launch (its
   // physics scalars go by value); the host source stays valid (it is the handle's)
@@ -561,6 +592,29 @@ extern "C" int hg_set_env_props(void* sim, const float* friction, const float* b
   hipLaunchKernelGGL(k_set_props, dim3((s->S.n + 255) / 256), dim3(256), 0, (hipStream_t)stream, s->S, friction,
                      base_mass);
   return hipGetLastError() == hipSuccess ? HG_OK : fail(s, HG_ERR_HIP, "k_set_props launch failed");
+}
+
+// ---- hand-written actuator profiles: [N,12] row-major -> the SoA regions
+__global__ void k_set_actuator_props(HgState S, const float* __restrict__ kp_scale, const float* __restrict__ kd_scale,
+                                     const float* __restrict__ armature_add) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= S.n) return;
+  for (int j = 0; j < HG_ND; j++) {
+    if (kp_scale) S.kp_scale[j * S.np + e] = kp_scale[(size_t)e * HG_ND + j];
+    if (kd_scale) S.kd_scale[j * S.np + e] = kd_scale[(size_t)e * HG_ND + j];
+    if (armature_add) S.armature_add[j * S.np + e] = armature_add[(size_t)e * HG_ND + j];
+  }
+}
+
+extern "C" int hg_set_actuator_props(void* sim, const float* kp_scale, const float* kd_scale, const float* armature_add,
+                                     void* stream) {
+  Sim* s = (Sim*)sim;
+  if (!s) return HG_ERR_ARG;
+  s->actuator_props = 1;  // sticky: K_step reads the regions from now on
+  if (!kp_scale && !kd_scale && !armature_add) return HG_OK;
+  hipLaunchKernelGGL(k_set_actuator_props, dim3((s->S.n + 255) / 256), dim3(256), 0, (hipStream_t)stream, s->S,
+                     kp_scale, kd_scale, armature_add);
+  return hipGetLastError() == hipSuccess ? HG_OK : fail(s, HG_ERR_HIP, "k_set_actuator_props launch failed");
 }
 
 #ifndef HG_SRC_HASH

@@ -67,6 +67,11 @@ struct HgState {
   const hg_model* model;  // device copy
   float* cmd_range;       // [0..1] the live lin_vel_x command range (HG_T_CMD_RANGE_X, read when
                           // cfg.cmd_curriculum), [2] the mean terrain level the latest resetting launch folded
+  // per-env actuator model (hg_cfg.actuator_rand, hg_set_actuator_props), each [12][np]: K_step's
+  // per-env variant runs kp * kp_scale, kd * kd_scale, armature + armature_add; the default one reads none
+  float* kp_scale;
+  float* kd_scale;
+  float* armature_add;
 };
 
 // what the statistics block of the post launch needs for the command curriculum and the curriculum
@@ -138,6 +143,7 @@ __host__ __device__ inline u4 philox4x32_10(u4 c, uint32_t k0, uint32_t k1) {
 enum HgRngPurpose : uint32_t {
   RNG_ACT_DELAY = 1, RNG_ACT_NOISE = 2, RNG_OBS_NOISE = 3, RNG_CMD = 4, RNG_PUSH = 5,
   RNG_RESET_DOF = 6, RNG_RESET_ROOT = 7, RNG_TERRAIN = 8,
+  RNG_ACTUATOR = 10,  // 9 is the rollout's action sample (hg_rollout.hip)
 };
 
 // uniform in [0,1): 24 high bits

@@ -1272,6 +1272,48 @@ __global__ void __launch_bounds__(64 * WIN_ROWS) k_window_stats(HgWindow A, HgWi
   for (int k = lane; k < T.width; k += 64) h0[hist + k] = fr[k];
 }
 
+// Per-episode actuator randomisation (hg_cfg.actuator_rand, BUILD-DEFINED; include/hgsim.h): the envs
+// the launch just reset get new kp / kd scales, motor strength and added armature, so every episode
+// trains against its own actuator model.  A launch of its own after the post kernels (nothing is
+// inserted into k_post_step / k_post; launched only when the option is on), one lane per env.
+// Which envs: mode 0 (hg_post) the reset flags the launch wrote; mode 1 (hg_reset_masked) the mask,
+// all envs when NULL — not reset_buf, which unmasked envs still hold from the previous step.
+// Draws: purpose RNG_ACTUATOR at the launch's counter, blocks 0-2 kp, 3-5 kd, 6-8 strength, 9-11
+// armature, joint j = 4 b' + i from word i.  Every product and sum is rounded on its own (contraction
+// is off in act_draw), so a float32 replay of the formula gives the same bits.
+__device__ __forceinline__ float act_draw(const float* range, uint32_t word) {
+#pragma clang fp contract(off)
+  const float span = (range[1] - range[0]) * u01(word);
+  return range[0] + span;
+}
+__global__ void __launch_bounds__(256) k_actuator_draw(HgState S, uint64_t counter, int mode,
+                                                        const uint8_t* __restrict__ mask) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= S.n) return;
+  if (mode == 0 ? !S.reset_buf[e] : (mask && !mask[e])) return;
+  const hg_cfg* cfg = S.cfg;
+  const int np = S.np;
+  for (int b = 0; b < 3; b++) {
+    const u4 rp = rng4(cfg, e, counter, b, RNG_ACTUATOR), rd = rng4(cfg, e, counter, 3 + b, RNG_ACTUATOR);
+    const u4 rm = rng4(cfg, e, counter, 6 + b, RNG_ACTUATOR), ra = rng4(cfg, e, counter, 9 + b, RNG_ACTUATOR);
+    const uint32_t wp[4] = {rp.x, rp.y, rp.z, rp.w}, wd[4] = {rd.x, rd.y, rd.z, rd.w};
+    const uint32_t wm[4] = {rm.x, rm.y, rm.z, rm.w}, wa[4] = {ra.x, ra.y, ra.z, ra.w};
+    for (int i = 0; i < 4; i++) {
+      const int j = 4 * b + i;
+      const float sm = act_draw(cfg->act_strength_range, wm[i]);  // scales the whole PD law: folds into both
+      S.kp_scale[j * np + e] = act_draw(cfg->act_kp_range, wp[i]) * sm;
+      S.kd_scale[j * np + e] = act_draw(cfg->act_kd_range, wd[i]) * sm;
+      S.armature_add[j * np + e] = act_draw(cfg->act_armature_range, wa[i]);
+    }
+  }
+}
+
+extern "C" int hg_launch_actuator_draw(const HgState* S, uint64_t counter, int mode, const uint8_t* mask,
+                                       hipStream_t stream) {
+  hipLaunchKernelGGL(k_actuator_draw, dim3((S->n + 255) / 256), dim3(256), 0, stream, *S, counter, mode, mask);
+  return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
 extern "C" int hg_launch_post(const HgState* S, const hg_cfg* hcfg, uint64_t counter, int mode, const uint8_t* mask,
                               float* frame_obs, float* frame_priv, HgWindow obs, HgWindow priv, float inv_len_s,
                               int ep_slot, HgSink sink, HgCurriculum cur, hipStream_t stream) {

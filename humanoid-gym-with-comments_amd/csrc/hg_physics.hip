@@ -593,8 +593,11 @@ __device__ __forceinline__ void place_contact(EnvSh& E, const Cand& C, bool act,
 }  // namespace
 
 // FIXED = asset.fix_base_link, a compile-time constant so the factorised size and every
-// floating-base branch resolve at compile time
-template <bool FIXED>
+// floating-base branch resolve at compile time.  ACT = per-env actuator model (hg_cfg.actuator_rand /
+// hg_set_actuator_props): the prologue stages kp * kp_scale, kd * kd_scale and armature +
+// armature_add of its env instead of the shared values (36 loads per env per launch, nothing in
+// the substep loop changes); a template parameter, so the default kernel is the code it was
+template <bool FIXED, bool ACT>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) k_step(HgState S, const float* __restrict__ actions_in, uint64_t step_counter, const StepParams P) {
   __shared__ EnvSh shm[2];
   const int half = threadIdx.x >> 5;
@@ -660,10 +663,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   // PD constants of this lane's joint staged in LDS for all substeps; the position target is
   // constant over the policy step
   if (l < 12) {
-    E.pd_kp[l] = cfg->kp[l];
-    E.pd_kd[l] = cfg->kd[l];
+    if (ACT) {  // one f32 operation each (x * 1.0f and x + 0.0f are exact: the neutral rows give the default kernel's bits)
+      E.pd_kp[l] = cfg->kp[l] * S.kp_scale[l * np + e];
+      E.pd_kd[l] = cfg->kd[l] * S.kd_scale[l * np + e];
+      E.pd_arm[l] = M->armature[l + 1] + S.armature_add[l * np + e];
+    } else {
+      E.pd_kp[l] = cfg->kp[l];
+      E.pd_kd[l] = cfg->kd[l];
+      E.pd_arm[l] = M->armature[l + 1];
+    }
     E.pd_lim[l] = cfg->torque_limit[l];
-    E.pd_arm[l] = M->armature[l + 1];
     E.pd_tgt[l] = E.act[l] * cfg->action_scale + cfg->default_dof_pos[l];
   }
   for (int i = l; i < 18 * 20; i += 32) (&E.L[0][0])[i] = 0.f;  // the left-right cross block stays zero
@@ -1320,7 +1329,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 }
 
 extern "C" int hg_launch_step(const HgState* S, const hg_cfg* hcfg, const float* actions, uint64_t step_counter,
-                              hipStream_t stream) {
+                              int per_env_actuators, hipStream_t stream) {
   const int grid = (S->n + 1) / 2;  // env pairs (env_order: rebuilt by the post launch, hg_envlogic.hip)
   StepParams P;
   P.dt = hcfg->sim_dt;
@@ -1338,9 +1347,8 @@ extern "C" int hg_launch_step(const HgState* S, const hg_cfg* hcfg, const float*
   P.vs = hcfg->hf_vertical_scale;
   P.border = hcfg->hf_border;
   P.hf = hcfg->heightfield;
-  if (hcfg->fix_base_link)
-    hipLaunchKernelGGL(k_step<true>, dim3(grid), dim3(64), 0, stream, *S, actions, step_counter, P);
-  else
-    hipLaunchKernelGGL(k_step<false>, dim3(grid), dim3(64), 0, stream, *S, actions, step_counter, P);
+  auto* k = hcfg->fix_base_link ? (per_env_actuators ? k_step<true, true> : k_step<true, false>)
+                                : (per_env_actuators ? k_step<false, true> : k_step<false, false>);
+  hipLaunchKernelGGL(k, dim3(grid), dim3(64), 0, stream, *S, actions, step_counter, P);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }

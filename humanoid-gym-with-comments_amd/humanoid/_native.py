@@ -73,7 +73,10 @@ class HgCfg(ctypes.Structure):
         ("feet_body", i32 * 2), ("knee_body", i32 * 2), ("ref_idx", i32 * 6), ("yaw_roll_idx", i32 * 4),
         ("seed", ctypes.c_uint64),
         ("curriculum", i32), ("terrain_rows", i32), ("terrain_cols", i32), ("terrain_env_length", f32),
-        ("max_episode_length_s", f32), ("env_offset", i32), ("terrain_origins", ctypes.c_void_p),
+        ("max_episode_length_s", f32), ("env_offset", i32),
+        ("actuator_rand", i32), ("act_kp_range", f32 * 2), ("act_kd_range", f32 * 2), ("act_strength_range", f32 * 2),
+        ("act_armature_range", f32 * 2),
+        ("terrain_origins", ctypes.c_void_p),
         ("cmd_curriculum", i32), ("cmd_max_curriculum", f32),
     ]
 
@@ -91,7 +94,8 @@ TENSOR_IDS = [
     "FEET_AIR_TIME", "LAST_CONTACTS", "FEET_HEIGHT", "LAST_FEET_Z", "ENV_FRICTION", "BODY_MASS",
     "PUSH_FORCE", "PUSH_TORQUE", "BASE_LIN_VEL", "BASE_ANG_VEL", "PROJ_GRAVITY", "BASE_EULER",
     "REF_DOF_POS", "ENV_ORIGINS", "EP_STATS", "CONTACT_LAMBDA", "NONFINITE", "TERRAIN_LEVEL", "TERRAIN_TYPE",
-    "EP_STATS_RING", "ROWS_DROPPED", "ENV_ROWS", "ENV_ORDER", "CMD_RANGE_X", "CURRICULUM_RING",
+    "EP_STATS_RING", "ROWS_DROPPED", "ENV_ROWS", "ENV_ORDER",
+    "KP_SCALE", "KD_SCALE", "ARMATURE_ADD", "CMD_RANGE_X", "CURRICULUM_RING",
 ]
 EP_RING = 64  # HG_EP_RING
 T = {name: i for i, name in enumerate(TENSOR_IDS)}
@@ -100,7 +104,7 @@ T = {name: i for i, name in enumerate(TENSOR_IDS)}
 EXPORTS = ["hg_arena_bytes", "hg_create", "hg_destroy", "hg_last_error", "hg_tensor", "hg_step",
            "hg_post", "hg_set_rollout_sink", "hg_ep_stats_slot", "hg_obs_head", "hg_obs_window_advance", "hg_update_cfg", "hg_reset_masked",
            "hg_set_command_range_x", "hg_publish_terrain_level", "hg_set_dof_state_indexed", "hg_set_root_state_indexed",
-           "hg_set_root_state", "hg_set_env_props",
+           "hg_set_root_state", "hg_set_env_props", "hg_set_actuator_props",
            "hg_measure_heights", "hg_gae_scan", "hg_gae_stats_len", "hg_gae_normalize", "hg_adam_step", "hg_adam_chunk", "hg_kl_mean", "hg_kl_lr_rule",
            "hg_rollout_act", "hg_rollout_act_head", "hg_rollout_act_tail", "hg_rollout_env", "hg_gather_rows", "hg_gather_rows_ex", "hg_gather_stacked", "hg_ppo_loss", "hg_ppo_loss_lr", "hg_ppo_loss_scratch", "hg_ppo_loss_backward",
            "hg_mlp_act_backward", "hg_mlp_act_backward_scratch", "hg_colsum_jobs", "hg_linear_skinny_supported",
@@ -192,6 +196,8 @@ def load_library(path=LIB_PATH):
     L.hg_set_root_state.argtypes = [vp, vp, vp]
     L.hg_set_env_props.restype = ctypes.c_int
     L.hg_set_env_props.argtypes = [vp, vp, vp, vp]
+    L.hg_set_actuator_props.restype = ctypes.c_int
+    L.hg_set_actuator_props.argtypes = [vp, vp, vp, vp, vp]
     L.hg_gae_scan.restype = ctypes.c_int
     L.hg_gae_scan.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                               ctypes.c_float, ctypes.c_int, vp]

@@ -171,6 +171,14 @@ class XBotLCfg(BaseConfig):
         max_push_vel_xy_final = 1.0
         max_push_ang_vel_final = 1.0
         dynamic_randomization = 0.02
+        # per-episode actuator randomisation (BUILD-DEFINED; the reference has none): at every reset
+        # an env draws, per joint, a kp scale, a kd scale, a motor strength (scales the whole PD law
+        # before the torque clip) and an added rotor inertia (brackets the MJCF's 0.01)
+        randomize_actuators = False
+        kp_range = [0.8, 1.2]
+        kd_range = [0.8, 1.2]
+        motor_strength_range = [0.9, 1.1]
+        added_armature_range = [0.0, 0.02]
 
     class commands:
         curriculum = False

@@ -131,6 +131,13 @@ def build_hg_cfg(cfg, num_envs, sim_dt, seed, model_js, heightfield=None, hf_sha
     # command curriculum (update_command_curriculum, humanoid_env.py:1097-1106)
     c.cmd_curriculum = int(bool(getattr(cfg.commands, "curriculum", False)))
     c.cmd_max_curriculum = float(getattr(cfg.commands, "max_curriculum", 0.0))
+    # per-episode actuator randomisation (BUILD-DEFINED, include/hgsim.h hg_cfg.actuator_rand)
+    dr = cfg.domain_rand
+    c.actuator_rand = int(bool(getattr(dr, "randomize_actuators", False)))
+    for dst, name, default in ((c.act_kp_range, "kp_range", (1.0, 1.0)), (c.act_kd_range, "kd_range", (1.0, 1.0)),
+                               (c.act_strength_range, "motor_strength_range", (1.0, 1.0)),
+                               (c.act_armature_range, "added_armature_range", (0.0, 0.0))):
+        dst[0], dst[1] = getattr(dr, name, default)
     aux = dict(feet=feet, knees=knees, dof_names=dofs, body_names=bodies, kp=kp, kd=kd, torque_limits=tl,
                default_dof_pos=dd, limits=limits, velocity=velocity, scales=scales)
     return c, aux
@@ -321,6 +328,11 @@ class XBotLFreeEnv(BaseTask):
         # (max_command_x, mean terrain level), rows as _ep_ring's
         self._cmd_range = self._view(T["CMD_RANGE_X"])
         self._curriculum_ring = self._view(T["CURRICULUM_RING"])
+        # the per-env actuator model K_step runs with domain_rand.randomize_actuators or after
+        # set_actuator_props: factors on the shared kp / kd, rotor inertia added to the model's armature
+        self.kp_scale = self._view(T["KP_SCALE"])
+        self.kd_scale = self._view(T["KD_SCALE"])
+        self.armature_add = self._view(T["ARMATURE_ADD"])
         self.nonfinite_count = self._view(T["NONFINITE"])
         # constraint rows / contact points the solver's row budget dropped, per env, summed over
         # substeps (diagnostic; 0 in normal operation)
@@ -399,8 +411,8 @@ class XBotLFreeEnv(BaseTask):
         self.forward_vec = torch.tensor([1.0, 0.0, 0.0], device=self.device).repeat(self.num_envs, 1)
         self.commands_scale = torch.tensor([self.obs_scales.lin_vel, self.obs_scales.lin_vel, self.obs_scales.ang_vel],
                                            device=self.device)
-        self.p_gains = torch.tensor(self._aux["kp"], device=self.device).repeat(self.num_envs, 1)
-        self.d_gains = torch.tensor(self._aux["kd"], device=self.device).repeat(self.num_envs, 1)
+        self._base_p_gains = torch.tensor(self._aux["kp"], device=self.device).repeat(self.num_envs, 1)
+        self._base_d_gains = torch.tensor(self._aux["kd"], device=self.device).repeat(self.num_envs, 1)
         self.torque_limits = torch.tensor(self._aux["torque_limits"], device=self.device)
         self.default_dof_pos = torch.tensor(self._aux["default_dof_pos"], device=self.device).unsqueeze(0)
         self.default_joint_pd_target = self.default_dof_pos.clone()
@@ -470,6 +482,18 @@ class XBotLFreeEnv(BaseTask):
         return self._priv_views[self.hg.hg_obs_head(self.sim)]
 
     @property
+    def p_gains(self):
+        """[N, 12] stiffness each env runs with: the configured gains x kp_scale (the configured
+        gains themselves unless actuators are randomised or set_actuator_props was called)."""
+        on = self._per_env_actuators or self._hgcfg.actuator_rand
+        return self._base_p_gains * self.kp_scale if on else self._base_p_gains
+
+    @property
+    def d_gains(self):
+        on = self._per_env_actuators or self._hgcfg.actuator_rand
+        return self._base_d_gains * self.kd_scale if on else self._base_d_gains
+
+    @property
     def dof_state(self):
         """[N*D, 2] (pos, vel) — a copy: the sim stores dof state SoA."""
         return torch.stack((self.dof_pos, self.dof_vel), dim=-1).reshape(-1, 2)
@@ -528,6 +552,26 @@ class XBotLFreeEnv(BaseTask):
         """Set the live lin_vel_x range (checkpoint resume), ordered on the current stream."""
         N.check(self.hg.hg_set_command_range_x(self.sim, float(lo), float(hi), self._stream()), self.sim)
         self.command_ranges["lin_vel_x"] = [float(lo), float(hi)]
+
+    _per_env_actuators = False
+
+    def set_actuator_props(self, kp_scale=None, kd_scale=None, armature_add=None):
+        """Hand-written actuator profiles: [num_envs, 12] factors on the configured kp / kd and
+        rotor inertia added to the model's armature (None leaves that one alone), ordered on the
+        current stream.  From this call on K_step runs its per-env variant, whether or not
+        domain_rand.randomize_actuators is on (with it on, an env's rows are redrawn at its reset)."""
+        ptrs, keep = [], []
+        for t in (kp_scale, kd_scale, armature_add):
+            if t is None:
+                ptrs.append(None)
+                continue
+            t = torch.as_tensor(t, dtype=torch.float32, device=self.device).contiguous()
+            if t.shape != (self.num_envs, 12):
+                raise ValueError(f"set_actuator_props: [{self.num_envs}, 12] arrays, got {tuple(t.shape)}")
+            keep.append(t)
+            ptrs.append(ctypes.c_void_p(t.data_ptr()))
+        N.check(self.hg.hg_set_actuator_props(self.sim, *ptrs, self._stream()), self.sim)
+        self._per_env_actuators = True
 
     def _launch_reset(self, mask_u8):
         mp = ctypes.c_void_p(mask_u8.data_ptr()) if mask_u8 is not None else None

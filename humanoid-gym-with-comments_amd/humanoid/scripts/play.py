@@ -39,6 +39,7 @@ def play(args, steps=100):
     env_cfg.terrain.max_init_terrain_level = 5
     env_cfg.noise.add_noise = True
     env_cfg.domain_rand.push_robots = False
+    env_cfg.domain_rand.randomize_actuators = False
     env_cfg.noise.noise_level = 0.5
     train_cfg.seed = 123145
     env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)

@@ -78,6 +78,7 @@ def make_cfg(profile, num_envs, duration, self_collisions=True):
     cfg.domain_rand.randomize_friction = False
     cfg.domain_rand.randomize_base_mass = False
     cfg.domain_rand.push_robots = False
+    cfg.domain_rand.randomize_actuators = False
     cfg.domain_rand.dynamic_randomization = 0.0
     cfg.commands.heading_command = False
     cfg.commands.resampling_time = duration + 1.0

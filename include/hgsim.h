@@ -139,6 +139,26 @@ typedef struct hg_cfg {
                                          * max_episode_length * dt) */
   int32_t env_offset;                   /* global id of this shard's env 0 (data parallel): every Philox
                                          * draw is keyed by the global env id */
+  /* per-episode actuator randomisation (BUILD-DEFINED, like the push curriculum: the reference has
+   * no such option; 0 = off, and then nothing changes).  K_step's PD law runs with per-env values,
+   * one f32 operation each from the shared ones:
+   *   kp_e = kp[j] * HG_T_KP_SCALE[e][j],  kd_e = kd[j] * HG_T_KD_SCALE[e][j],
+   *   armature_e = model.armature[j + 1] + HG_T_ARMATURE_ADD[e][j]
+   * (scales, not absolute gains, so hg_update_cfg may still change kp / kd under them; kd_e also
+   * enters the implicit-damping term; torque_limit stays shared: motor strength scales the PD law
+   * before the clip).  When actuator_rand != 0 every post / reset launch ends with one more kernel
+   * that redraws the rows of exactly the envs that launch reset (hg_post: reset_buf; hg_reset_masked:
+   * the mask, all envs when NULL) from the Philox stream, purpose 10, key (global env id, the launch's
+   * counter, block): for joint j = 4 b' + i, word i of block b' gives s_p in act_kp_range, of block
+   * 3 + b' s_d in act_kd_range, of block 6 + b' the motor strength s_m in act_strength_range, of block
+   * 9 + b' a in act_armature_range, each lo + (hi - lo) * u01(word); stored are kp_scale = s_p * s_m,
+   * kd_scale = s_d * s_m, armature_add = a.  K_step reads the three regions when actuator_rand != 0
+   * or after hg_set_actuator_props.  When actuator_rand != 0, hg_create / hg_update_cfg refuse a
+   * range with lo > hi, a scale bound <= 0 and a negative armature bound; none of the fields sizes
+   * the arena, so hg_update_cfg may change them all, the flag included.  (The fields sit here, not at
+   * the end of the struct: the command curriculum's two stay the last.) */
+  int32_t actuator_rand;
+  float act_kp_range[2], act_kd_range[2], act_strength_range[2], act_armature_range[2];
   const float* terrain_origins;         /* device [rows, cols, 3], caller-owned */
   /* command curriculum (update_command_curriculum, humanoid_env.py:1097-1106; commands.curriculum /
    * max_curriculum, humanoid_config.py): when cmd_curriculum != 0 the lin_vel_x bounds of every
@@ -197,6 +217,9 @@ enum hg_tensor_id {
                             wave-balancing sort key) */
   HG_T_ENV_ORDER,        /* [N] int32, read-only diagnostic: the env K_step's half-wave k runs, as the latest post
                             launch sorted it (a permutation of each XCD's env range; identity without balancing) */
+  HG_T_KP_SCALE,         /* [N,12] f32, SoA: per-env factor on cfg.kp (hg_cfg.actuator_rand); hg_create sets 1 */
+  HG_T_KD_SCALE,         /* [N,12] f32, SoA: per-env factor on cfg.kd; hg_create sets 1 */
+  HG_T_ARMATURE_ADD,     /* [N,12] f32, SoA: per-env rotor inertia added to model.armature[1..12]; hg_create sets 0 */
   HG_T_CMD_RANGE_X,      /* [2] f32: the live lin_vel_x command range (command_ranges["lin_vel_x"]); hg_create sets it
                             to cfg.cmd_lin_x, hg_update_cfg leaves it alone, hg_set_command_range_x writes it */
   HG_T_CURRICULUM_RING,  /* [HG_EP_RING, 2] f32: (max_command_x, mean terrain level) as each post/reset launch left
@@ -270,6 +293,13 @@ int hg_set_root_state(void* sim, const float* root, void* stream);
  * _process_rigid_shape_props / _process_rigid_body_props, humanoid_env.py:528-553,578-584):
  * friction, base_mass: device [N] f32 (either may be NULL) */
 int hg_set_env_props(void* sim, const float* friction, const float* base_mass, void* stream);
+/* hand-written actuator profiles (BUILD-DEFINED, hg_cfg.actuator_rand): stream-ordered write of
+ * HG_T_KP_SCALE / HG_T_KD_SCALE / HG_T_ARMATURE_ADD from device [N,12] row-major f32 arrays (any may
+ * be NULL: that region is left alone).  The call is sticky on the handle: every later hg_step reads
+ * the three regions even when cfg.actuator_rand == 0 (nothing redraws them then; with
+ * actuator_rand != 0 an env's rows are redrawn at its next reset). */
+int hg_set_actuator_props(void* sim, const float* kp_scale, const float* kd_scale, const float* armature_add,
+                          void* stream);
 
 /* ---- measured heights (replaces _get_heights, humanoid_env.py:949-985) ----
  * points_xy: device f32 [P,2] sample points in the base frame (the _init_height_points grid,
