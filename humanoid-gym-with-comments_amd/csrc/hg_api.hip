@@ -79,6 +79,10 @@ int dtype_of(int id) {
 // shared by both tables, >= 26 and >= F - 1 of each.
 int win_advance(const hg_cfg* c) { return std::max(26, std::max(c->frame_stack, c->c_frame_stack) - 1); }
 int win_frames(int F, const hg_cfg* c) { return F - 1 + win_advance(c); }
+// frame slot width of the privileged window: the 73 columns k_post_step / k_post write plus the
+// height columns the window kernel generates (hg_cfg.critic_heights, 0 = off)
+int priv_width(const hg_cfg* c) { return HG_PRIV1 + c->critic_heights; }
+bool height_count_ok(const hg_cfg* c) { return c->critic_heights >= 0 && c->critic_heights <= HG_MAX_HEIGHT_POINTS; }
 
 Layout make_layout(const hg_cfg* c) {
   Layout L;
@@ -99,7 +103,7 @@ Layout make_layout(const hg_cfg* c) {
   }
   // the observation histories: one sliding window per env row (hg_obs_window_frames)
   const size_t ob = (size_t)n * win_frames(c->frame_stack, c) * HG_OBS1 * 4;
-  const size_t pb = (size_t)n * win_frames(c->c_frame_stack, c) * HG_PRIV1 * 4;
+  const size_t pb = (size_t)n * win_frames(c->c_frame_stack, c) * priv_width(c) * 4;
   L.obs_buf = o; o += align256(ob);
   L.priv_buf = o; o += align256(pb);
   L.frame_obs = o; o += align256((size_t)n * HG_OBS1 * 4);
@@ -182,7 +186,7 @@ __global__ void k_init(HgState S) {
 extern "C" {
 
 size_t hg_arena_bytes(const hg_cfg* cfg) {
-  if (!cfg || cfg->num_envs <= 0) return 0;
+  if (!cfg || cfg->num_envs <= 0 || !height_count_ok(cfg)) return 0;
   return make_layout(cfg).bytes;
 }
 
@@ -218,6 +222,10 @@ int hg_create(const hg_cfg* cfg, const hg_model* model, void* arena, size_t aren
   if (cfg->cmd_curriculum && (cfg->max_episode_length <= 0 || !(cfg->cmd_max_curriculum >= 0.f)))
     return fail(nullptr, HG_ERR_ARG, "command curriculum needs max_episode_length > 0 and cmd_max_curriculum >= 0");
   if (const char* m = actuator_cfg_error(cfg)) return fail(nullptr, HG_ERR_ARG, m);
+  if (!height_count_ok(cfg))
+    return fail(nullptr, HG_ERR_ARG, "critic_heights must be in [0, HG_MAX_HEIGHT_POINTS (1024)]");
+  if (cfg->critic_heights > 0 && !cfg->critic_height_points)
+    return fail(nullptr, HG_ERR_ARG, "critic_heights > 0 needs the device sample grid critic_height_points");
   Sim* s = new Sim();
   s->cfg = *cfg;
   s->model = *model;
@@ -328,7 +336,7 @@ int hg_tensor(void* sim, int id, hg_desc* d) {
     case HG_T_OBS_BUF:  // the history windows: [N, (F - 1 + HW) * width]; the stack = columns
     case HG_T_PRIV_BUF: {  // [head * width, (head + F) * width) (hg_obs_head)
       const int64_t w = id == HG_T_OBS_BUF ? (int64_t)win_frames(s->cfg.frame_stack, &s->cfg) * HG_OBS1
-                                           : (int64_t)win_frames(s->cfg.c_frame_stack, &s->cfg) * HG_PRIV1;
+                                           : (int64_t)win_frames(s->cfg.c_frame_stack, &s->cfg) * priv_width(&s->cfg);
       d->ndim = 2;
       d->shape[0] = n; d->shape[1] = w;
       d->strides[0] = w; d->strides[1] = 1;
@@ -389,8 +397,8 @@ static int do_post(Sim* s, uint64_t counter, int mode, const uint8_t* mask, void
   const HgWindow wo = {(float*)(s->arena + s->L.obs_buf), (int64_t)win_frames(s->cfg.frame_stack, &s->cfg) * HG_OBS1,
                        HG_OBS1, s->cfg.frame_stack, head, shift ? old + 1 : -1};
   const HgWindow wp = {(float*)(s->arena + s->L.priv_buf),
-                       (int64_t)win_frames(s->cfg.c_frame_stack, &s->cfg) * HG_PRIV1, HG_PRIV1, s->cfg.c_frame_stack,
-                       head, shift ? old + 1 : -1};
+                       (int64_t)win_frames(s->cfg.c_frame_stack, &s->cfg) * priv_width(&s->cfg), priv_width(&s->cfg),
+                       s->cfg.c_frame_stack, head, shift ? old + 1 : -1};
   // a step's post launch takes the pending rollout sink (reset launches leave it pending)
   const HgSink sink = mode == 0 ? s->sink : HgSink{nullptr, nullptr, nullptr};
   if (mode == 0) s->sink = HgSink{nullptr, nullptr, nullptr};
@@ -449,7 +457,8 @@ int hg_update_cfg(void* sim, const hg_cfg* cfg, void* stream) {
   if (cfg->num_envs != o.num_envs || cfg->frame_stack != o.frame_stack || cfg->c_frame_stack != o.c_frame_stack ||
       cfg->decimation != o.decimation || cfg->terrain_type != o.terrain_type || cfg->hf_rows != o.hf_rows ||
       cfg->hf_cols != o.hf_cols || cfg->heightfield != o.heightfield || cfg->terrain_origins != o.terrain_origins ||
-      cfg->terrain_rows != o.terrain_rows || cfg->terrain_cols != o.terrain_cols)
+      cfg->terrain_rows != o.terrain_rows || cfg->terrain_cols != o.terrain_cols ||
+      cfg->critic_heights != o.critic_heights || cfg->critic_height_points != o.critic_height_points)
     return fail(s, HG_ERR_ARG, "hg_update_cfg: layout fields cannot change after hg_create");
   if (cfg->pgs_iterations < 0 || cfg->pgs_iterations > 1000 || !(cfg->sim_dt > 0.f))
     return fail(s, HG_ERR_ARG, "hg_update_cfg: bad solver parameters");
@@ -538,21 +547,8 @@ __global__ void k_heights(HgState S, const float* __restrict__ pts, int P, float
   if (t >= (int64_t)S.n * P) return;
   const int e = (int)(t / P), k = (int)(t % P);
   const hg_cfg* cfg = S.cfg;
-  if (cfg->terrain_type == 0 || cfg->heightfield == nullptr) { out[t] = 0.f; return; }
-  // quat_apply_yaw (utils/math.py:39-43): keep (z, w), normalise, rotate
-  const float qz = S.root[5 * S.np + e], qw = S.root[6 * S.np + e];
-  const float nrm = fmaxf(sqrtf(qz * qz + qw * qw), 1e-9f);
-  const f3 p = quat_apply(0.f, 0.f, qz / nrm, qw / nrm, mk(pts[2 * k], pts[2 * k + 1], 0.f));
-  const float x = p.x + S.root[0 * S.np + e] + cfg->hf_border;
-  const float y = p.y + S.root[1 * S.np + e] + cfg->hf_border;
-  long long px = (long long)(x / cfg->hf_horizontal_scale), py = (long long)(y / cfg->hf_horizontal_scale);
-  px = px < 0 ? 0 : (px > cfg->hf_rows - 2 ? cfg->hf_rows - 2 : px);
-  py = py < 0 ? 0 : (py > cfg->hf_cols - 2 ? cfg->hf_cols - 2 : py);
-  const int16_t* hf = cfg->heightfield;
-  const int C = cfg->hf_cols;
-  int h = hf[px * C + py];
-  h = min(h, (int)hf[(px + 1) * C + py]);
-  h = min(h, (int)hf[px * C + py + 1]);
+  const int h = hg_terrain_sample(cfg, S.root[5 * S.np + e], S.root[6 * S.np + e], S.root[0 * S.np + e],
+                                  S.root[1 * S.np + e], pts[2 * k], pts[2 * k + 1]);
   out[t] = (float)h * cfg->hf_vertical_scale;
 }
 

@@ -30,7 +30,7 @@ struct HgState {
   float* last_root_vel;   // [6][np]
   float* commands;        // [4][np]
   float* obs;             // [n][(frame_stack - 1 + HW) * 47] history windows (hg_api.hip)
-  float* priv;            // [n][(c_frame_stack - 1 + HW) * 73]
+  float* priv;            // [n][(c_frame_stack - 1 + HW) * (73 + cfg.critic_heights)]
   float* rew;             // [np]
   uint8_t* reset_buf;     // [np]
   uint8_t* time_out;      // [np]
@@ -106,7 +106,8 @@ struct HgSink {
 };
 
 // one observation history window table for the post launch: row e = win + e * rowlen, frame slots of
-// `width` floats; this launch writes the new frame into slot head + frames - 1, zeroes slots
+// `width` floats (the privileged table's 73 + hg_cfg.critic_heights: its source frame stays 73 wide,
+// the window kernel generates the rest); this launch writes the new frame into slot head + frames - 1, zeroes slots
 // head .. head + frames - 2 of reset envs and, when shift_src >= 0, first moves slots
 // shift_src .. shift_src + frames - 2 to 0 .. frames - 2
 struct HgWindow {
@@ -192,6 +193,31 @@ __device__ __forceinline__ f3 quat_apply(float qx, float qy, float qz, float qw,
   f3 xyz = mk(qx, qy, qz);
   f3 t = 2.0f * cross(xyz, v);
   return v + qw * t + cross(xyz, t);
+}
+
+// Terrain height under a base-frame sample point (_get_heights, humanoid_env.py:949-985): the point
+// yaw-rotated (quat_apply_yaw, utils/math.py:39-43: keep (z, w), normalise, rotate), offset by the
+// base position and the border, quantised to the heightfield grid (truncated toward zero, clipped
+// to [0, rows-2] x [0, cols-2], so the three reads stay inside the field), the minimum of three
+// neighbours, in heightfield units: the caller multiplies by vertical_scale (a product rounded on
+// its own); 0 on a plane.  qz, qw: the root quaternion's z, w; bx, by: root x, y.  Shared by
+// k_heights (hg_api.hip) and the privileged frame's height columns (hg_envlogic.hip).
+__device__ __forceinline__ int hg_terrain_sample(const hg_cfg* cfg, float qz, float qw, float bx, float by, float ptx,
+                                                 float pty) {
+  if (cfg->terrain_type == 0 || cfg->heightfield == nullptr) return 0;
+  const float nrm = fmaxf(sqrtf(qz * qz + qw * qw), 1e-9f);
+  const f3 p = quat_apply(0.f, 0.f, qz / nrm, qw / nrm, mk(ptx, pty, 0.f));
+  const float x = p.x + bx + cfg->hf_border;
+  const float y = p.y + by + cfg->hf_border;
+  long long px = (long long)(x / cfg->hf_horizontal_scale), py = (long long)(y / cfg->hf_horizontal_scale);
+  px = px < 0 ? 0 : (px > cfg->hf_rows - 2 ? cfg->hf_rows - 2 : px);
+  py = py < 0 ? 0 : (py > cfg->hf_cols - 2 ? cfg->hf_cols - 2 : py);
+  const int16_t* hf = cfg->heightfield;
+  const int C = cfg->hf_cols;
+  int h = hf[px * C + py];
+  h = min(h, (int)hf[(px + 1) * C + py]);
+  h = min(h, (int)hf[px * C + py + 1]);
+  return h;
 }
 
 // K_step's env order for wave balancing (HgState::env_order; k_step maps its blocks through it):

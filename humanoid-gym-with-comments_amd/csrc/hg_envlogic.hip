@@ -1174,7 +1174,26 @@ __global__ void __launch_bounds__(256) k_cmd_curriculum(HgState S, uint64_t coun
 // when any env reset) and clears the accumulators; with the command curriculum or the terrain-level
 // extra on (HgCurriculum) it also writes the widened lin_vel_x range and the launch's
 // (max_command_x, mean terrain level) ring row.
+//
+// HEIGHTS (hg_cfg.critic_heights = P > 0, BUILD-DEFINED; include/hgsim.h): table B's frame slots are
+// 73 + P wide while its source frame stays [n][73]; the wave that appends env e's privileged frame
+// also generates the P height columns behind the 73 copied ones, straight into the window slot: the
+// root pose is read once per wave (it is the post-reset pose: k_post_step / k_post and
+// k_cmd_curriculum ran before this launch), lane l takes points l, l + 64, ... (three int16 gathers
+// each; neighbouring points of one grid row hit neighbouring cells of one heightfield row, the
+// output row is contiguous per wave).  Shift and zero-on-reset run over the slot width, so they
+// cover the height columns.  The default instantiation is the kernel without any of this.
 constexpr int WIN_ROWS = 4;  // (env, table) rows per k_window_stats block, one wave each
+// column 73 + k: float32 in exactly this order (two subtractions, clamp, one multiply, clamp), every
+// operation rounded on its own, so a float32 replay gives the same bits
+__device__ __forceinline__ float height_column(float z, int sample, float vertical_scale, float scale, float clip) {
+#pragma clang fp contract(off)
+  const float h = (float)sample * vertical_scale;
+  const float d = (z - 0.5f) - h;
+  const float c = fminf(fmaxf(d, -1.f), 1.f) * scale;
+  return fminf(fmaxf(c, -clip), clip);
+}
+template <bool HEIGHTS>
 __global__ void __launch_bounds__(64 * WIN_ROWS) k_window_stats(HgWindow A, HgWindow B, const float* __restrict__ frame_a,
                                                       const float* __restrict__ frame_b,
                                                       const uint8_t* __restrict__ reset, int n, float* ep_stats,
@@ -1184,7 +1203,7 @@ __global__ void __launch_bounds__(64 * WIN_ROWS) k_window_stats(HgWindow A, HgWi
                                                       const float* __restrict__ rew,
                                                       const uint8_t* __restrict__ time_out, int nsink,
                                                       const hg_cfg* __restrict__ cfg, float* __restrict__ cmd_range,
-                                                      HgCurriculum cur) {
+                                                      HgCurriculum cur, const float* __restrict__ root, int np) {
   static_assert(64 * WIN_ROWS == HG_ORD_T, "the order blocks use the window block's threads");
   // blocks 0 .. nsort - 1: the next K_step's env order (hg_common.h), first so that they start
   // with the launch and run beside the window rows
@@ -1258,7 +1277,9 @@ __global__ void __launch_bounds__(64 * WIN_ROWS) k_window_stats(HgWindow A, HgWi
   const bool a = b < n;
   const HgWindow& T = a ? A : B;
   const int e = a ? b : b - n;
-  const float* __restrict__ fr = (a ? frame_a : frame_b) + (size_t)e * T.width;
+  // the source frame's width: the slot's, except table B's with the height columns on
+  const int srcw = (HEIGHTS && !a) ? HG_PRIV1 : T.width;
+  const float* __restrict__ fr = (a ? frame_a : frame_b) + (size_t)e * srcw;
   float* __restrict__ row = T.win + (size_t)e * T.rowlen;
   const int hist = (T.frames - 1) * T.width;  // the older frames of the new stack
   const bool rs = reset[e] != 0;
@@ -1269,7 +1290,17 @@ __global__ void __launch_bounds__(64 * WIN_ROWS) k_window_stats(HgWindow A, HgWi
   } else if (rs) {
     for (int k = lane; k < hist; k += 64) h0[k] = 0.f;
   }
-  for (int k = lane; k < T.width; k += 64) h0[hist + k] = fr[k];
+  for (int k = lane; k < srcw; k += 64) h0[hist + k] = fr[k];
+  if (HEIGHTS && !a) {
+    const int P = T.width - HG_PRIV1;  // = cfg->critic_heights (hg_api.hip priv_width)
+    const float bx = root[0 * np + e], by = root[1 * np + e], z = root[2 * np + e];
+    const float qz = root[5 * np + e], qw = root[6 * np + e];
+    const float vs = cfg->hf_vertical_scale, scale = cfg->critic_height_scale, clip = cfg->clip_observations;
+    const float* __restrict__ pts = cfg->critic_height_points;
+    float* __restrict__ out = h0 + hist + HG_PRIV1;
+    for (int k = lane; k < P; k += 64)
+      out[k] = height_column(z, hg_terrain_sample(cfg, qz, qw, bx, by, pts[2 * k], pts[2 * k + 1]), vs, scale, clip);
+  }
 }
 
 // Per-episode actuator randomisation (hg_cfg.actuator_rand, BUILD-DEFINED; include/hgsim.h): the envs
@@ -1336,8 +1367,13 @@ extern "C" int hg_launch_post(const HgState* S, const hg_cfg* hcfg, uint64_t cou
   const int nsort = S->balance ? 8 : 0;
   const int nsink = sink.rew ? (n + 64 * WIN_ROWS - 1) / (64 * WIN_ROWS) : 0;
   const int g = nsort + nsink + (2 * n + WIN_ROWS - 1) / WIN_ROWS + 1;
-  hipLaunchKernelGGL(k_window_stats, dim3(g), dim3(64 * WIN_ROWS), 0, stream, obs, priv, frame_obs, frame_priv,
-                     S->reset_buf, n, S->ep_stats, inv_len_s, ep_slot, S->env_rows, S->env_order, nsort, sink, S->rew,
-                     S->time_out, nsink, S->cfg, S->cmd_range, cur);
+  if (hcfg->critic_heights > 0)
+    hipLaunchKernelGGL(k_window_stats<true>, dim3(g), dim3(64 * WIN_ROWS), 0, stream, obs, priv, frame_obs, frame_priv,
+                       S->reset_buf, n, S->ep_stats, inv_len_s, ep_slot, S->env_rows, S->env_order, nsort, sink, S->rew,
+                       S->time_out, nsink, S->cfg, S->cmd_range, cur, S->root, S->np);
+  else
+    hipLaunchKernelGGL(k_window_stats<false>, dim3(g), dim3(64 * WIN_ROWS), 0, stream, obs, priv, frame_obs, frame_priv,
+                       S->reset_buf, n, S->ep_stats, inv_len_s, ep_slot, S->env_rows, S->env_order, nsort, sink, S->rew,
+                       S->time_out, nsink, S->cfg, S->cmd_range, cur, S->root, S->np);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }

@@ -76,6 +76,7 @@ class HgCfg(ctypes.Structure):
         ("max_episode_length_s", f32), ("env_offset", i32),
         ("actuator_rand", i32), ("act_kp_range", f32 * 2), ("act_kd_range", f32 * 2), ("act_strength_range", f32 * 2),
         ("act_armature_range", f32 * 2),
+        ("critic_heights", i32), ("critic_height_scale", f32), ("critic_height_points", ctypes.c_void_p),
         ("terrain_origins", ctypes.c_void_p),
         ("cmd_curriculum", i32), ("cmd_max_curriculum", f32),
     ]

@@ -174,6 +174,14 @@ _DW_SPLIT = {(128, 256): 32, (128, 128): 16, (256, 512): 4, (128, 705): 8, (512,
 WGRAD_TR = os.environ.get("HG_WGRAD_TR", "1") != "0"
 _GEMM_DW = {(512, 705): [(8191, 0), (_BIG_ROWS, (49, 32))],
             (256, 768): [(8191, 0), (_BIG_ROWS, (49, 64))]} if WGRAD_TR else {}
+# terrain.critic_heights (default grid): the critic's first-layer weight gradient is 768 x 780.
+# hipBLASLt's default kernel for it (no TunableOp entry) ran 351 us per call in the update's trace,
+# 2.8 ms per iteration (768 x 219: 76 us).  The update's learn time per iteration at 4096 envs, one
+# runner per route alternating on one box, three repetitions (ms): hipBLASLt 13.44-13.50, torch bmm
+# split-K 8 12.67-12.93 (32: 13.24-13.34), k_wgrad_tr tile 54 x 64 slices 12.67-12.70, 49 x 64
+# 12.65-12.78, 54 x 32 12.51-12.60, 49 x 32 12.44-12.50 (profiles/critic_heights/wgrad_routes.json).
+if WGRAD_TR:
+    _GEMM_DW[(768, 780)] = [(8191, 0), (_BIG_ROWS, (49, 32))]
 # the other products' best tr tiles (probe); HG_WGRAD_TR=all routes all of them, a list such as
 # "256x512,128x705" only those: measured 0.25 ms per iteration slower for "all" on one box
 # (profiles/r4_ab), so none is routed by default
@@ -289,6 +297,11 @@ if os.environ.get("HG_X6_APF", "1") == "0":
 # (53.9).  Same-box bench A/B (HG_OCC_TILES=0, three alternations): 5.469-5.485 -> 5.495-5.503 M
 # env-steps/s.  The 128 -> 256 input gradients (actor and critic, 24576 rows) moved from the f32 tile
 # 16 (24.0 us) to tile 31 (20.2 us, profiles/r6_gemm/occ_sweep2.json).
+# terrain.critic_heights (default grid: 187 points): the critic's first layer reads 3 x (73 + 187) =
+# 780 columns.  It takes the tiles of the 219 -> 768 layer it replaces (the same n, the K loop 3.6 x
+# as long; tile choice at K = 780 not measured); other grids (e.g. 3 x 3: K = 246) keep torch's
+# addmm + ELU like every shape absent from the table.
+_GEMM_FWD[(780, 768)] = _GEMM_FWD[(219, 768)]
 _GEMM_DX = {(256, 512): [(_BIG, 22)], (128, 256): [(_BIG, 31)], (256, 768): [(_BIG, 31)], (128, 128): [(_BIG, 5)]}
 GEMM = os.environ.get("HG_GEMM", "1") != "0"
 # The bf16-split tiles read B (the weight) from an image split once per MLP call

@@ -285,6 +285,14 @@ class OnPolicyRunner:
 
     def load(self, path, load_optimizer=True):
         d = torch.load(path, map_location=self.device, weights_only=True)
+        # a checkpoint trained with another critic input width (terrain.critic_heights on / off, or
+        # another sample grid) does not fit this env: say so before any tensor is copied
+        w = d["model_state_dict"].get("critic.0.weight")
+        have = self.alg.actor_critic.critic[0].in_features
+        if w is not None and w.shape[1] != have:
+            raise ValueError(f"checkpoint {path}: its critic takes {w.shape[1]} inputs, this env's critic {have} "
+                             "(num_privileged_obs); terrain.critic_heights and the measured_points grid must be "
+                             "what the checkpoint was trained with")
         self.alg.actor_critic.load_state_dict(d["model_state_dict"])
         if load_optimizer:
             self.alg.optimizer.load_state_dict(d["optimizer_state_dict"])

@@ -723,9 +723,14 @@ class PPO:
                 self.capture_error = "another rank's capture failed"
             warnings.warn(f"PPO: the in-graph all-reduce could not be captured ({self.capture_error}); "
                           "using two graphs per minibatch with the all-reduce between them")
-        with _capturing(ga, "global"):
+        # data parallel: thread_local here too.  The process group's watchdog thread polls the events
+        # of the collectives issued so far (the ok-flag all-reduce above completes just before these
+        # captures); under "global" its event query is refused, which invalidates the capture and
+        # ends the process from the watchdog
+        mode = "thread_local" if self._dp else "global"
+        with _capturing(ga, mode):
             self._mb_backward(self._idx)
-        with _capturing(gb, "global", pool=ga.pool()):
+        with _capturing(gb, mode, pool=ga.pool()):
             self._mb_step()
         self._graphs = (ga, gb, mb, self._storage_key())
         self.update_graph = "two"

@@ -72,6 +72,13 @@ class XBotLCfg(BaseConfig):
         border_size = 25
         curriculum = False
         measure_heights = False
+        # BUILD-DEFINED (the reference's concatenation, humanoid_env.py:871-874, replaces the 73-wide
+        # privileged frame by the stacked actor observation plus the heights and changes its width
+        # mid-run): True appends the len(x) * len(y) measured heights, as
+        # clip(z - 0.5 - h, -1, 1) * obs_scales.height_measurements, to every privileged frame, so
+        # the critic sees the terrain; num_privileged_obs becomes c_frame_stack * (73 + P) on the env
+        # and on its cfg instance.  Independent of measure_heights.  Sampled at the post-reset pose.
+        critic_heights = False
         measured_points_x = [-0.8, -0.7, -0.6, -0.5, -0.4, -0.3, -0.2, -0.1, 0.0, 0.1, 0.2, 0.3, 0.4,
                              0.5, 0.6, 0.7, 0.8]
         measured_points_y = [-0.5, -0.4, -0.3, -0.2, -0.1, 0.0, 0.1, 0.2, 0.3, 0.4, 0.5]

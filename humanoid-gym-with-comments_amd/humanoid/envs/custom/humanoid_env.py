@@ -10,6 +10,11 @@ stacking) launched on the current stream — no host synchronisation.
 Tensor attributes (root_states, dof_pos, contact_forces, rigid_state, commands, rew_buf, ...)
 are zero-copy views into the simulator's SoA arena, so they read and write like the reference's
 gymtorch-wrapped tensors (``root_states[:, 3:7]``, ``dof_pos[env_ids] = ...``).
+
+``terrain.critic_heights`` (BUILD-DEFINED; the reference's concatenation, humanoid_env.py:871-874,
+changes the privileged frame's width mid-run) widens every privileged frame by the measured
+terrain heights under the sample grid, written on the device by the post launch's window kernel;
+``num_privileged_obs`` then is ``c_frame_stack * (73 + P)`` here and on ``cfg.env``.
 """
 import ctypes
 
@@ -33,9 +38,20 @@ assert REWARD_NAMES == sorted(REWARD_NAMES)
 _TORCH_DTYPES = {0: torch.float32, 1: torch.int64, 2: torch.uint8, 3: torch.int32}
 
 
+def critic_height_grid(cfg):
+    """The base-frame sample grid of terrain.critic_heights as float32 [P, 2], x-major (the first two
+    columns of _init_height_points, humanoid_env.py:314-328); None with the option off."""
+    if not getattr(cfg.terrain, "critic_heights", False):
+        return None
+    x = np.asarray(cfg.terrain.measured_points_x, np.float32)
+    y = np.asarray(cfg.terrain.measured_points_y, np.float32)
+    return np.stack([np.repeat(x, len(y)), np.tile(y, len(x))], axis=1)
+
+
 def build_hg_cfg(cfg, num_envs, sim_dt, seed, model_js, heightfield=None, hf_shape=(0, 0), terrain_origins=None,
-                 terrain_shape=(0, 0)):
-    """XBotLCfg -> hg_cfg (include/hgsim.h).  Returns (hg_cfg, aux dict)."""
+                 terrain_shape=(0, 0), height_points=None):
+    """XBotLCfg -> hg_cfg (include/hgsim.h).  Returns (hg_cfg, aux dict).  height_points: device
+    pointer to critic_height_grid(cfg) (terrain.critic_heights; the grid itself is aux["height_grid"])."""
     c = N.HgCfg()
     c.num_envs = num_envs
     c.decimation = cfg.control.decimation
@@ -138,7 +154,13 @@ def build_hg_cfg(cfg, num_envs, sim_dt, seed, model_js, heightfield=None, hf_sha
                                (c.act_strength_range, "motor_strength_range", (1.0, 1.0)),
                                (c.act_armature_range, "added_armature_range", (0.0, 0.0))):
         dst[0], dst[1] = getattr(dr, name, default)
-    aux = dict(feet=feet, knees=knees, dof_names=dofs, body_names=bodies, kp=kp, kd=kd, torque_limits=tl,
+    # measured heights in the privileged frame (BUILD-DEFINED, include/hgsim.h hg_cfg.critic_heights)
+    grid = critic_height_grid(cfg)
+    if grid is not None:
+        c.critic_heights = len(grid)
+        c.critic_height_scale = cfg.normalization.obs_scales.height_measurements
+        c.critic_height_points = height_points
+    aux = dict(height_grid=grid, feet=feet, knees=knees, dof_names=dofs, body_names=bodies, kp=kp, kd=kd, torque_limits=tl,
                default_dof_pos=dd, limits=limits, velocity=velocity, scales=scales)
     return c, aux
 
@@ -242,8 +264,13 @@ class XBotLFreeEnv(BaseTask):
         if self.custom_origins:
             self.terrain_origins = torch.from_numpy(self.terrain.env_origins).to(self.device).to(torch.float).contiguous()
             to_ptr, to_shape = self.terrain_origins.data_ptr(), tuple(self.terrain_origins.shape[:2])
+        # terrain.critic_heights: the sample grid lives on the device for the env's lifetime (the
+        # window kernel of every post / reset launch reads it through hg_cfg.critic_height_points)
+        grid = critic_height_grid(self.cfg)
+        self._critic_height_xy = None if grid is None else torch.from_numpy(grid).to(self.device).contiguous()
+        hp_ptr = None if grid is None else self._critic_height_xy.data_ptr()
         self._hgcfg, self._aux = build_hg_cfg(self.cfg, self.num_envs, self.sim_dt, seed, js, hf_ptr, hf_shape,
-                                              to_ptr, to_shape)
+                                              to_ptr, to_shape, hp_ptr)
         nbytes = self.hg.hg_arena_bytes(ctypes.byref(self._hgcfg))
         self._arena = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
         off = (-self._arena.data_ptr()) % 256
@@ -264,6 +291,13 @@ class XBotLFreeEnv(BaseTask):
         self.penalised_contact_indices = torch.tensor([0], dtype=torch.long, device=self.device)
         self.termination_contact_indices = torch.tensor([0], dtype=torch.long, device=self.device)
         self._wrap_all()
+        if self._hgcfg.critic_heights > 0:
+            # terrain.critic_heights: the privileged widths follow the window's frame slots (73 + P),
+            # on the env and on its cfg instance: the runner, ActorCritic and RolloutStorage size
+            # themselves from them
+            self.num_privileged_obs = int(self.cfg.env.c_frame_stack) * self._priv_width
+            self.cfg.env.single_num_privileged_obs = self._priv_width
+            self.cfg.env.num_privileged_obs = self.num_privileged_obs
         self._get_env_origins()
         self._randomize_props()
 
@@ -301,6 +335,7 @@ class XBotLFreeEnv(BaseTask):
         wo, wp = self._obs_win.shape[1] // (fo - 1 + hw), self._priv_win.shape[1] // (fp - 1 + hw)
         self._obs_views = tuple(self._obs_win[:, h * wo:(h + fo) * wo] for h in range(hw))
         self._priv_views = tuple(self._priv_win[:, h * wp:(h + fp) * wp] for h in range(hw))
+        self._priv_width = wp
         self.rew_buf = self._view(T["REW_BUF"])
         self._reset_u8 = self._view(T["RESET_BUF"])
         self._timeout_u8 = self._view(T["TIME_OUT_BUF"])

@@ -41,6 +41,7 @@ extern "C" {
 #define HG_MAX_PAIRS 16     /* self-collision capsule pairs */
 #define HG_NUM_REWARDS 22
 #define HG_MAX_TENSORS 32
+#define HG_MAX_HEIGHT_POINTS 1024  /* hg_cfg.critic_heights: sample points per env in the privileged frame */
 /* solver warm-start impulses per env: 3 per ground candidate, 3 per pair, joint limits, joint friction */
 #define HG_LAMW (HG_MAX_CONTACTS * 3 + HG_MAX_PAIRS * 3 + 2 * HG_MAX_DOF)
 
@@ -159,6 +160,28 @@ typedef struct hg_cfg {
    * the end of the struct: the command curriculum's two stay the last.) */
   int32_t actuator_rand;
   float act_kp_range[2], act_kd_range[2], act_strength_range[2], act_armature_range[2];
+  /* measured terrain heights as columns of the privileged frame (terrain.critic_heights,
+   * BUILD-DEFINED: the reference's concatenation, humanoid_env.py:871-874, replaces the privileged
+   * frame by the stacked actor observation plus the heights and so changes its width mid-run; here
+   * the frame keeps its 73 columns and gains P = critic_heights more, 0 = off, and then nothing
+   * changes).  Column 73 + k of env e's newest frame =
+   *   clip(clip((z - 0.5) - h[e][k], -1, 1) * critic_height_scale, +- clip_observations)
+   * in float32 in exactly this order (two subtractions, clamp, one multiply, clamp; no noise: the
+   * reference adds none to privileged observations), z = root z of env e and h[e][k] the terrain
+   * height under sample point k by the rule of hg_measure_heights (0 on a plane), both at the pose
+   * the frame's other columns are written from, i.e. AFTER the launch's resets, in hg_post and in
+   * hg_reset_masked.  (A deliberate deviation: the reference measures before reset_idx and observes
+   * after it, which pairs a resetting env's new z with the terrain under its old position.)  The
+   * columns are generated by the wave that appends the env's frame to its HG_T_PRIV_BUF window: no
+   * launch and no buffer is added.  The window's frame slots are 73 + P wide, stacked, shifted and
+   * zeroed on reset over the full width.  critic_heights and critic_height_points lay out the arena:
+   * hg_create refuses a count < 0 or > HG_MAX_HEIGHT_POINTS and a positive count with a NULL grid,
+   * hg_update_cfg refuses a change of either; critic_height_scale may change.  (The fields sit here
+   * for the same reason as the actuator fields above.) */
+  int32_t critic_heights;               /* P, the number of sample points; 0 = off */
+  float critic_height_scale;            /* normalization.obs_scales.height_measurements */
+  const float* critic_height_points;    /* device f32 [P, 2] base-frame sample grid, caller-owned (the
+                                         * _init_height_points grid, :314-328, x-major) */
   const float* terrain_origins;         /* device [rows, cols, 3], caller-owned */
   /* command curriculum (update_command_curriculum, humanoid_env.py:1097-1106; commands.curriculum /
    * max_curriculum, humanoid_config.py): when cmd_curriculum != 0 the lin_vel_x bounds of every
@@ -193,7 +216,8 @@ enum hg_tensor_id {
   HG_T_OBS_BUF,          /* [N, (frame_stack - 1 + HW) * 47] observation history window per env: the
                             stacked policy input is columns [h * 47, (h + frame_stack) * 47), h =
                             hg_obs_head() (a strided [N, frame_stack*47] view; HW = hg_obs_window_advance) */
-  HG_T_PRIV_BUF,         /* [N, (c_frame_stack - 1 + HW) * 73], its stack columns [h * 73, (h + c_frame_stack) * 73) */
+  HG_T_PRIV_BUF,         /* [N, (c_frame_stack - 1 + HW) * W], its stack columns [h * W, (h + c_frame_stack) * W),
+                            W = 73 + hg_cfg.critic_heights (73 unless the height columns are on) */
   HG_T_REW_BUF,          /* [N] */
   HG_T_RESET_BUF,        /* [N] bool */
   HG_T_TIME_OUT_BUF,     /* [N] bool */
@@ -267,7 +291,8 @@ int hg_obs_head(void* sim);
 int hg_obs_window_advance(void* sim);
 /* Runtime parameter update (curricula, e.g. the push-recovery ramp of config 5): copies *cfg into
  * the handle and, stream-ordered, into the device copy the kernels read.  Fields that size or
- * lay out the arena (num_envs, frame stacks, terrain tables, decimation) must be unchanged. */
+ * lay out the arena (num_envs, frame stacks, terrain tables, decimation, critic_heights and its
+ * grid pointer) must be unchanged. */
 int hg_update_cfg(void* sim, const hg_cfg* cfg, void* stream);
 /* replaces reset_idx() (humanoid_env.py:1109-1163) for an explicit device mask [N] (u8). */
 int hg_reset_masked(void* sim, const uint8_t* mask, uint64_t counter, void* stream);
