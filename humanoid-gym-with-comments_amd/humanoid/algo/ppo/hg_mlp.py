@@ -442,12 +442,13 @@ _SCOPE = None  # {(weight address, trans): image} while an image_scope is active
 
 
 @contextlib.contextmanager
-def image_scope(specs, dev, pairs=()):
+def image_scope(specs, dev, pairs=(), alone=()):
     """The weight images of several fusable MLPs (``specs``: [(net, rows)]) built in ONE launch
     for the MLP calls inside the block — one image launch per PPO minibatch instead of one per
     network; ``pairs`` [(net_a, net_b, rows)]: the stacked first-layer image of mlp_pair_forward
-    (those nets' own first-layer images are then not built).  The weights must not change inside
-    the block."""
+    (those nets' own first-layer images are then not built, except for the nets in ``alone``:
+    paired nets the block also calls on their own, as PPO's mirrored actor pass).  The weights
+    must not change inside the block."""
     global _SCOPE
     jobs, keys = [], []
     paired = set()
@@ -461,7 +462,7 @@ def image_scope(specs, dev, pairs=()):
         if not fusable(net):
             continue
         params = _params(net)
-        first = 1 if id(net) in paired else 0
+        first = 1 if id(net) in paired and not any(net is a for a in alone) else 0
         for _, _, W, trans, R, K in _image_specs(params, len(params) // 2, rows, True, first):
             key = (W.data_ptr(), trans)
             if key not in keys:

@@ -50,7 +50,7 @@ def _rank():
 class OnPolicyRunner:
     def __init__(self, env, train_cfg, log_dir=None, device="cpu"):
         self.cfg = train_cfg["runner"]
-        self.alg_cfg = train_cfg["algorithm"]
+        self.alg_cfg = dict(train_cfg["algorithm"])  # a copy: the symmetry tables are filled in below
         self.policy_cfg = train_cfg["policy"]
         self.all_cfg = train_cfg
         self.wandb_run_name = (datetime.now().strftime("%b%d_%H-%M-%S") + "_" + train_cfg["runner"]["experiment_name"]
@@ -66,6 +66,15 @@ class OnPolicyRunner:
         policy_cls = {"ActorCritic": ActorCritic}[self.cfg["policy_class_name"]]
         actor_critic = policy_cls(env.num_obs, num_critic_obs, env.num_actions, **self.policy_cfg).to(self.device)
         alg_cls = {"PPO": PPO}[self.cfg["algorithm_class_name"]]
+        if self.alg_cfg.get("sym_loss"):
+            # the symmetry loss without hand-written tables: XBot-L's mirror (utils/symmetry.py)
+            # and the env's frame stacking
+            if self.alg_cfg.get("obs_permutation") is None or self.alg_cfg.get("act_permutation") is None:
+                from humanoid.utils.symmetry import xbotl_mirror
+                self.alg_cfg["obs_permutation"], self.alg_cfg["act_permutation"] = xbotl_mirror()
+            if not self.alg_cfg.get("frame_stack"):
+                self.alg_cfg["frame_stack"] = int(getattr(getattr(getattr(env, "cfg", None), "env", None),
+                                                          "frame_stack", 0) or 0)
         self.alg = alg_cls(actor_critic, device=self.device, **self.alg_cfg)
         self.num_steps_per_env = self.cfg["num_steps_per_env"]
         self.save_interval = self.cfg["save_interval"]
@@ -171,6 +180,8 @@ class OnPolicyRunner:
                 # for this iteration's whole update and leave the GPU idle while the host queues
                 # the next rollout
                 means3 = (losses[0], losses[1], losses[3])
+                if self.alg.sym_loss:  # the last minibatch's symmetry loss rides along
+                    means3 += (losses[2],)
                 if all(torch.is_tensor(x) for x in means3):  # device 0-d means (graphed update)
                     dev_means = torch.stack(means3)
                     host_means = torch.empty(dev_means.shape, dtype=torch.float32, pin_memory=True)
@@ -195,6 +206,8 @@ class OnPolicyRunner:
             self.last_iteration_stats = dict(collection_time=collection_time, learn_time=learn_time,
                                              value_loss=mean_value_loss, surrogate_loss=mean_surrogate_loss,
                                              lin_vel_loss=mean_base_lin_vel_loss)
+            if self.alg.sym_loss:
+                self.last_iteration_stats["sym_loss"] = float(sym_loss)
             if self.log_dir is not None:
                 # the rollout's finished episodes in step order, env order within a step (the
                 # order the reference appends them in): one host read per iteration, after the
@@ -221,10 +234,12 @@ class OnPolicyRunner:
         ev[2].synchronize()
         if copied is not None:
             copied.synchronize()
-        v, s, lv = [float(x) for x in host_means.tolist()]
+        v, s, lv, *sym = [float(x) for x in host_means.tolist()]
         self.last_iteration_stats = dict(collection_time=ev[0].elapsed_time(ev[1]) * 1e-3,
                                          learn_time=ev[1].elapsed_time(ev[2]) * 1e-3,
                                          value_loss=v, surrogate_loss=s, lin_vel_loss=lv)
+        if sym:  # only with the symmetry loss on
+            self.last_iteration_stats["sym_loss"] = sym[0]
 
     def log(self, locs, width=90, pad=45):
         self.tot_timesteps += self.num_steps_per_env * self.env.num_envs

@@ -31,6 +31,7 @@ from .actor_critic import ActorCritic, _DiagGaussian
 from .hg_adam import HgAdam
 from . import hg_mlp
 from . import hg_loss
+from . import hg_sym
 from .hg_loss import ppo_loss
 from .rollout_storage import RolloutStorage, gather_rows
 
@@ -160,8 +161,8 @@ class PPO:
         # global id of storage row 0 (data parallel: the runner sets the env shard's offset), so the
         # action noise of a sharded run is the single run's
         self.row_offset = 0
-        # the minibatch loss and its gradient on the fused HIP kernels (hg_loss.py); the symmetry
-        # loss configuration keeps the op-by-op expression
+        # the minibatch loss and its gradient on the fused HIP kernels (hg_loss.py, hg_sym.py); False
+        # selects the op-by-op expression of _losses (with sym_loss: eager, the mirror matrices)
         self.use_fused_loss = True
         self.defer_values = True
         self._rollout_seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self._on_device else 0
@@ -178,6 +179,10 @@ class PPO:
         self.base_lin_vel_coef = base_lin_vel_coef
         self.sym_loss = sym_loss
         self.sym_coef = sym_coef
+        # device (perm int32, sign f32) forms of the two mirror tables for the fused route
+        # (hg_sym.py); None: the op-by-op expression of _losses with the matrices below
+        self._sym_tables = None
+        self._sym_last = None  # the last minibatch's symmetry loss on the fused route (0-d device tensor)
         if self.sym_loss:
             # mirror matrices built on the policy's device (the reference hard-codes .cuda(), ppo.py:96,103)
             n_act = len(act_permutation)
@@ -192,6 +197,34 @@ class PPO:
             self.obs_perm_mat = torch.zeros(len(stack), len(stack), device=device)
             for i, perm in enumerate(stack):
                 self.obs_perm_mat[int(abs(perm))][i] = 1.0 if perm >= 0 else -1.0
+            self._sym_tables = self._build_sym_tables(obs_permutation, stack, act_permutation)
+            if self._sym_tables is not None:
+                self._sym_last = torch.zeros((), dtype=torch.float32, device=device)
+
+    def _build_sym_tables(self, obs_permutation, stack, act_permutation):
+        """((obs perm, obs sign), (act perm, act sign)) device tables of the symmetry loss's fused
+        route from the stacked observation table and the action table, or None when they do not
+        validate (the op-by-op path then runs with the matrices, as before).  Same rule as the
+        matrices: source column ``int(abs(p))``, negative iff ``p < 0``; index 0 is negated by a
+        small negative entry such as ``-0.0001``.  One difference from the reference: it takes
+        ``np.sign(p)``, so a literal ``0`` entry is a zero column there and ``+1`` in
+        ``obs_perm_mat`` here; a signed gather cannot express a zero column, so a table with a
+        literal ``0`` is left to the op-by-op path (the shipped XBot-L tables have none).
+        Validated: both tables in range, the action table a permutation, and
+        ``len(obs_permutation) * frame_stack`` equal to the actor's input width."""
+        if not self._on_device:
+            return None
+        first = next((m for m in self.actor_critic.actor if isinstance(m, nn.Linear)), None)
+        n_obs, n_act = len(obs_permutation), len(act_permutation)
+        if first is None or len(stack) != first.in_features:
+            return None
+        if any(p == 0 for p in list(obs_permutation) + list(act_permutation)):
+            return None
+        if any(not 0 <= int(abs(p)) < n_obs for p in obs_permutation):
+            return None
+        if sorted(int(abs(p)) for p in act_permutation) != list(range(n_act)):
+            return None
+        return hg_sym.device_table(stack, self.device), hg_sym.device_table(act_permutation, self.device)
 
     @property
     def learning_rate(self):
@@ -472,7 +505,22 @@ class PPO:
 
     @property
     def _fused_loss(self):
-        return self._on_device and self.use_fused_loss and not self.sym_loss
+        """Whether the minibatch loss runs on the fused HIP kernels (and the update may be
+        captured).  With ``sym_loss`` only when the mirror tables validated (_build_sym_tables),
+        the policy is fp32 and the actor runs on the build's own MLP kernels: the mirror, the
+        second actor pass and the symmetry loss then run in _losses_fused.  A bf16 policy with the
+        symmetry loss keeps the eager op-by-op path."""
+        if not (self._on_device and self.use_fused_loss):
+            return False
+        return not self.sym_loss or self._sym_fused
+
+    @property
+    def _sym_fused(self):
+        """The symmetry loss runs on the fused route (hg_sym.py) inside _losses_fused."""
+        ac = self.actor_critic
+        return (self.sym_loss and self._on_device and self.use_fused_loss and self._sym_tables is not None
+                and getattr(ac, "policy_dtype", "fp32") == "fp32" and getattr(ac, "fused_mlp", False)
+                and hg_mlp.fusable(ac.actor))
 
     def _losses_fused(self, obs_b, critic_b, lin_vel_b, actions_b, target_values_b, adv_b, returns_b, old_logp_b,
                       old_mu_b, old_sigma_b, stats_out=None, lr_rule=None):
@@ -485,9 +533,13 @@ class PPO:
         # stacked GEMM (hg_mlp.mlp_pair_forward) where it is routed
         pair = (own and obs_b.dtype == torch.float32 and obs_b.dim() == 2 and obs_b.stride(1) == 1
                 and hg_mlp.pair_ok(ac.actor, ac.base_lin_vel, obs_b.shape[0]))
+        sym = self._sym_fused
+        # the mirrored pass runs the actor on its own: its first-layer image joins the scope even
+        # when the unmirrored pass takes the stacked one (no second image launch)
         scope = (hg_mlp.image_scope([(ac.actor, obs_b.shape[0]), (ac.base_lin_vel, obs_b.shape[0]),
                                      (ac.critic, critic_b.shape[0])], obs_b.device,
-                                    pairs=[(ac.actor, ac.base_lin_vel, obs_b.shape[0])] if pair else ())
+                                    pairs=[(ac.actor, ac.base_lin_vel, obs_b.shape[0])] if pair else (),
+                                    alone=(ac.actor,) if sym and pair else ())
                  if own else contextlib.nullcontext())
         with scope:  # the three networks' weight images in one launch
             if pair:
@@ -497,12 +549,27 @@ class PPO:
                 est_lin_vel = ac.base_get_lin_vel(obs_b)
             ac.distribution = _DiagGaussian(mu, ac.std.expand_as(mu))
             value_b = ac.evaluate(critic_b)
+            if sym:
+                # ppo.py:199-200: the minibatch rows mirrored by a signed column gather (one pass
+                # instead of the [mb, 705] x [705, 705] product), then the actor on them
+                (o_perm, o_sign), _ = self._sym_tables
+                x = obs_b if obs_b.dtype == torch.float32 else obs_b.float()
+                mu_mirror = ac._mlp(ac.actor, hg_sym.mirror_rows(x, o_perm, o_sign))
         data = {"actions": actions_b, "old_logp": old_logp_b, "advantages": adv_b, "target_values": target_values_b,
                 "returns": returns_b, "old_mu": old_mu_b, "old_sigma": old_sigma_b,
                 "lin_vel_target": lin_vel_b if lin_vel_b.dtype == torch.float32 else lin_vel_b.float()}
-        return ppo_loss(mu, ac.std, value_b, est_lin_vel, data, self.clip_param, self.value_loss_coef,
-                        self.entropy_coef, self.base_lin_vel_coef, self.use_clipped_value_loss,
-                        stats_out=stats_out, accumulate=stats_out is not None, lr_rule=lr_rule)
+        out = ppo_loss(mu, ac.std, value_b, est_lin_vel, data, self.clip_param, self.value_loss_coef,
+                       self.entropy_coef, self.base_lin_vel_coef, self.use_clipped_value_loss,
+                       stats_out=stats_out, accumulate=stats_out is not None, lr_rule=lr_rule)
+        if not sym:
+            return out
+        # ppo.py:201-202, 208: + sym_coef * mean((mu - mirror_act @ act_perm_mat)^2); the unweighted
+        # mean of this (the last) minibatch is what update() returns (ppo.py:226)
+        a_perm, a_sign = self._sym_tables[1]
+        s_loss = hg_sym.sym_loss(mu, mu_mirror, a_perm, a_sign, self.sym_coef, sym_out=self._sym_last)
+        if stats_out is not None:
+            return out + s_loss
+        return out[0] + s_loss, out[1]
 
     def _losses(self, obs_b, critic_b, lin_vel_b, actions_b, target_values_b, adv_b, returns_b, old_logp_b):
         """Minibatch loss (ppo.py:155-214).  The reference calls actor_critic.act() here and
@@ -548,8 +615,10 @@ class PPO:
             self.optimizer.step()
 
     def update(self, sync=True):
-        """ppo.py:140-226.  Returns the mean value / surrogate / sym / lin-vel losses as floats; with
-        sync=False (device path) the means stay on the device (0-d tensors; no host wait)."""
+        """ppo.py:140-226.  Returns the mean value / surrogate / lin-vel losses and, in the third
+        slot, the symmetry loss of the last minibatch (the reference's return, ppo.py:226: not a
+        mean; 0 with the option off) as floats; with sync=False (device path) they stay on the
+        device (0-d tensors; no host wait)."""
         if self._on_device and self.use_graphs:
             return self._update_graphed(sync)
         out = self._update_eager()
@@ -594,7 +663,11 @@ class PPO:
                 mean_surrogate_loss += surrogate_loss.item()
                 mean_base_lin_vel_loss += base_lin_vel_loss.item()
         num_updates = self.num_learning_epochs * self.num_mini_batches
-        if sums is not None:
+        if sums is not None and self._sym_fused:
+            # the last minibatch's symmetry loss (ppo.py:226) rides in the same host read
+            (mean_value_loss, mean_surrogate_loss, mean_base_lin_vel_loss,
+             sym_loss) = torch.cat([sums, self._sym_last.view(1)]).tolist()
+        elif sums is not None:
             mean_value_loss, mean_surrogate_loss, mean_base_lin_vel_loss = sums.tolist()  # one host read
         mean_value_loss /= num_updates
         mean_surrogate_loss /= num_updates
@@ -820,8 +893,8 @@ class PPO:
         nmb = self.num_mini_batches
         batch = st.num_envs * st.num_transitions_per_env
         mb = batch // nmb
-        if self.sym_loss or (self._graphs is None and not self._graph_warm):
-            # warm-up (and the symmetry-loss configuration, which stays eager)
+        if (self.sym_loss and not self._fused_loss) or (self._graphs is None and not self._graph_warm):
+            # warm-up (and the symmetry loss on the op-by-op expression, which stays eager)
             cur = torch.cuda.current_stream()
             side = torch.cuda.Stream()
             side.wait_stream(cur)
@@ -852,6 +925,13 @@ class PPO:
         num_updates = self.num_learning_epochs * nmb
         means = self._sums / num_updates
         st.clear()
+        if self._sym_fused:
+            # the last minibatch's symmetry loss (ppo.py:226: not a mean), a copy so that the next
+            # replay does not change what the caller holds
+            if not sync:
+                return means[0], means[1], self._sym_last.clone(), means[2]
+            v, s, lv, sym = torch.cat([means, self._sym_last.view(1)]).tolist()  # the one host read
+            return v, s, sym, lv
         if not sync:
             return means[0], means[1], 0, means[2]
         v, s, lv = means.tolist()  # the one host read of the update

@@ -275,6 +275,13 @@ class XBotLCfgPPO(BaseConfig):
         num_mini_batches = 4
         desired_kl = 0.01
         max_grad_norm = 1.0
+        # mirror-symmetry loss (ppo.py:59-63, 197-208): sym_coef * mean((mu - mirrored mu of the
+        # mirrored observations)^2).  Tables None: the runner fills XBot-L's from
+        # humanoid/utils/symmetry.py and frame_stack from the env
+        sym_loss = False
+        sym_coef = 1.0
+        obs_permutation = None
+        act_permutation = None
 
     class runner:
         policy_class_name = "ActorCritic"

@@ -520,6 +520,39 @@ int64_t hg_ppo_loss_scratch(int64_t rows, int num_actions);
 int hg_ppo_loss_backward(const float* grad_loss, int64_t rows, int num_actions, float* grad_mu, float* grad_std,
                          float* grad_value, float* grad_lin_vel, void* stream);
 
+/* ---- mirror-symmetry loss (replaces ppo.py:197-202: the two products with the +-1 permutation
+ * matrices obs_perm_mat / act_perm_mat and (mu_batch - m_mirror_act).pow(2).mean()) ----
+ * A mirror table is a device int32 perm[width] and a device float32 sign[width] of +-1: column c
+ * of the mirrored row is sign[c] * column perm[c] of the row (the matrix of ppo.py:96-105 has its
+ * one entry of column c in row perm[c]).
+ * hg_mirror_rows: dst[r][c] = sign[c] * src[r][perm[c]] over [rows, width] float32 with row
+ * strides in elements (so either side may be a column slice of a wider table); 2 x rows x width x
+ * 4 B of traffic, row-contiguous stores, one launch, graph-capturable.  A perm entry outside
+ * [0, width) gives a zero column.  HG_ERR_ARG before any launch: a NULL pointer, rows <= 0,
+ * width <= 0, a stride below width, src == dst (not an in-place operation). */
+int hg_mirror_rows(const float* src, int64_t src_ld, float* dst, int64_t dst_ld, int64_t rows, int width,
+                   const int32_t* perm, const float* sign, void* stream);
+/* hg_sym_loss: with m[r][i] = sign[i] * mu_mirror[r][perm[i]] (the actor's mean on the mirrored
+ * observations, mirrored back, ppo.py:200-201) and d = mu - m over [rows, num_actions]:
+ *   sym_out[0]  = mean(d^2) over rows * num_actions            (ppo.py:202)
+ *   loss_out[0] = coef * sym_out[0]                             (its term of ppo.py:208)
+ *   grad_mu[r][i]           =            coef * 2 d[r][i] / (rows * num_actions)
+ *   grad_mirror[r][perm[i]] = -sign[i] * coef * 2 d[r][i] / (rows * num_actions)
+ * mu / mu_mirror: float32 rows with strides in elements; the gradients contiguous
+ * [rows, num_actions], unscaled: hg_sym_loss_backward multiplies both in place by the device
+ * scalar grad_loss.  perm must be a permutation of 0 .. num_actions - 1 (the caller checks: every
+ * grad_mirror element is then written exactly once, no atomics; entries outside the range are
+ * skipped).  d is one float32 subtraction; its squares are summed in float64, per-wave partials
+ * in scratch (>= hg_sym_loss_scratch() doubles), then in a fixed order: bitwise reproducible.
+ * Two launches + one for the backward; graph-capturable.  HG_ERR_ARG before any launch: a NULL
+ * pointer, rows <= 0, num_actions <= 0 or > HG_MAX_DOF, a stride below num_actions. */
+int hg_sym_loss(const float* mu, int64_t mu_ld, const float* mu_mirror, int64_t mu_mirror_ld, const int32_t* perm,
+                const float* sign, int64_t rows, int num_actions, double coef, float* loss_out, float* sym_out,
+                float* grad_mu, float* grad_mirror, double* scratch, void* stream);
+int64_t hg_sym_loss_scratch(int64_t rows, int num_actions);
+int hg_sym_loss_backward(const float* grad_loss, int64_t rows, int num_actions, float* grad_mu, float* grad_mirror,
+                         void* stream);
+
 /* ---- policy MLP backward: activation backward + bias gradient in one pass (replaces, per
  * Linear(+ELU) layer of actor_critic.py:36-149, torch's ELU backward and grad_bias = gh.sum(0))
  * gh = gy * elu'(h) with elu'(h) = 1 for y > 0, y + 1 otherwise (y = the layer's ELU output);
