@@ -164,44 +164,54 @@ def termination(contact_forces, ep_len, L: Layout, P):
     return reset | timeout, timeout
 
 
-def rewards(S, L: Layout, P):
+def rewards(S, L: Layout, P, dtype=f32):
     """The 22 _reward_* terms (humanoid_env.py:1170-1437).  S: dict of state arrays; mutates
     S['feet_air_time'], S['last_contacts'], S['feet_height'], S['last_feet_z'] like the reference.
-    Returns dict name -> term (unscaled)."""
+    Returns dict name -> term (unscaled).
+
+    dtype: the precision of the arithmetic (float32: the reference's).  With float64 the same code
+    is the high-precision reference of the same operation: the state is promoted on load, the
+    constants keep their float32 values, and every discrete decision (contact, stance, thresholds,
+    selections) is still taken in float32 on the float32 state, so both precisions walk the same
+    branches."""
     T = {}
-    q, qd, a = S["dof_pos"], S["dof_vel"], S["actions"]
-    la, lla = S["last_actions"], S["last_last_actions"]
-    cf, rs, root = S["contact_forces"], S["rigid_state"], S["root_states"]
-    blv, bav, pg, eul, cmd = S["base_lin_vel"], S["base_ang_vel"], S["projected_gravity"], S["base_euler_xyz"], S["commands"]
+    lo = lambda k: np.asarray(S[k]).astype(f32)        # noqa: E731  the float32 state: decisions
+    hi = lambda k: np.asarray(S[k]).astype(dtype)      # noqa: E731  the arithmetic
+    q, qd, a = hi("dof_pos"), hi("dof_vel"), hi("actions")
+    la, lla = hi("last_actions"), hi("last_last_actions")
+    cf, rs, root = hi("contact_forces"), hi("rigid_state"), hi("root_states")
+    blv, bav, pg, eul, cmd = hi("base_lin_vel"), hi("base_ang_vel"), hi("projected_gravity"), hi("base_euler_xyz"), hi("commands")
+    cf32, rs32, blv32, cmd32 = lo("contact_forces"), lo("rigid_state"), lo("base_lin_vel"), lo("commands")
     fe, kn = list(L.feet), list(L.knees)
     _, _, stance = gait(S["episode_length_buf"], P)
-    contact = cf[:, fe, 2] > 5.0
+    contact = cf32[:, fe, 2] > 5.0
     T["action_smoothness"] = (np.sum(np.square(la - a), 1) + np.sum(np.square(a + lla - 2 * la), 1)
                               + f32(0.05) * np.sum(np.abs(a), 1))
-    T["base_acc"] = np.exp(-np.linalg.norm(S["last_root_vel"] - root[:, 7:13], axis=1) * 3)
+    T["base_acc"] = np.exp(-np.linalg.norm(hi("last_root_vel") - root[:, 7:13], axis=1) * 3)
     mh = np.sum(rs[:, fe, 2] * stance, 1) / np.sum(stance, 1)
     T["base_height"] = np.exp(-np.abs(root[:, 2] - (mh - f32(0.05)) - f32(P.base_height_target)) * 100)
-    T["collision"] = np.sum(1.0 * (np.linalg.norm(cf[:, [L.base], :], axis=-1) > 0.1), 1)
-    jd = q - S["default_dof_pos"]
+    T["collision"] = np.sum(1.0 * (np.linalg.norm(cf32[:, [L.base], :], axis=-1) > 0.1), 1)
+    jd = q - hi("default_dof_pos")
     y = L.yaw_roll
     yr = np.linalg.norm(jd[:, [y[0], y[1]]], axis=1) + np.linalg.norm(jd[:, [y[2], y[3]]], axis=1)
     yr = np.clip(yr - f32(0.1), 0, 50)
     T["default_joint_pos"] = np.exp(-yr * 100) - f32(0.01) * np.linalg.norm(jd, axis=1)
-    T["dof_acc"] = np.sum(np.square((S["last_dof_vel"] - qd) / f32(P.dt)), 1)
+    T["dof_acc"] = np.sum(np.square((hi("last_dof_vel") - qd) / f32(P.dt)), 1)
     T["dof_vel"] = np.sum(np.square(qd), 1)
     # feet_air_time (mutates)
-    filt = contact | (stance != 0) | S["last_contacts"]
+    filt = contact | (stance != 0) | np.asarray(S["last_contacts"]).astype(bool)
     S["last_contacts"] = contact.copy()
-    first = (S["feet_air_time"] > 0) * filt
-    S["feet_air_time"] = S["feet_air_time"] + f32(P.dt)
+    first = (lo("feet_air_time") > 0) * filt
+    S["feet_air_time"] = hi("feet_air_time") + f32(P.dt)
     T["feet_air_time"] = np.sum(np.clip(S["feet_air_time"], 0, 0.5) * first, 1)
     S["feet_air_time"] = S["feet_air_time"] * ~filt
     # feet_clearance (mutates)
     fz = rs[:, fe, 2] - f32(0.05)
-    S["feet_height"] = S["feet_height"] + (fz - S["last_feet_z"])
+    fh32 = lo("feet_height") + ((rs32[:, fe, 2] - f32(0.05)) - lo("last_feet_z"))
+    S["feet_height"] = hi("feet_height") + (fz - hi("last_feet_z"))
     S["last_feet_z"] = fz
     swing = 1 - stance
-    rp = np.abs(S["feet_height"] - f32(P.target_feet_height)) < 0.01
+    rp = np.abs(fh32 - f32(P.target_feet_height)) < 0.01
     T["feet_clearance"] = np.sum(rp * swing, 1)
     S["feet_height"] = S["feet_height"] * ~contact
     T["feet_contact_forces"] = np.sum(np.clip(np.linalg.norm(cf[:, fe, :], axis=-1) - f32(P.max_contact_force), 0, 400), 1)
@@ -215,41 +225,42 @@ def rewards(S, L: Layout, P):
 
     T["feet_distance"] = dist_rew(rs[:, fe, :2], P.max_dist)
     T["foot_slip"] = np.sum(np.sqrt(np.linalg.norm(rs[:, fe, 10:12], axis=2)) * contact, 1)
-    diff = q - S["ref_dof_pos"]
+    diff = q - hi("ref_dof_pos")
     nd = np.linalg.norm(diff, axis=1)
     T["joint_pos"] = np.exp(-2 * nd) - f32(0.2) * np.clip(nd, 0, 0.5)
     T["knee_distance"] = dist_rew(rs[:, kn, :2], P.max_dist / 2)
-    sp, cm = np.abs(blv[:, 0]), np.abs(cmd[:, 0])
+    sp, cm = np.abs(blv32[:, 0]), np.abs(cmd32[:, 0])
     low, high = sp < 0.5 * cm, sp > 1.2 * cm
     des = ~(low | high)
-    mis = np.sign(blv[:, 0]) != np.sign(cmd[:, 0])
+    mis = np.sign(blv32[:, 0]) != np.sign(cmd32[:, 0])
     r = np.zeros(len(sp), f32)
     r[low] = -1.0
     r[high] = 0.0
     r[des] = 1.2
     r[mis] = -2.0
-    T["low_speed"] = r * (np.abs(cmd[:, 0]) > 0.1)
+    T["low_speed"] = r * (np.abs(cmd32[:, 0]) > 0.1)
     T["orientation"] = (np.exp(-np.sum(np.abs(eul[:, :2]), 1) * 10) + np.exp(-np.linalg.norm(pg[:, :2], axis=1) * 20)) / 2
-    T["torques"] = np.sum(np.square(S["torques"]), 1)
+    T["torques"] = np.sum(np.square(hi("torques")), 1)
     le = np.linalg.norm(cmd[:, :2] - blv[:, :2], axis=1)
     ae = np.abs(cmd[:, 2] - bav[:, 2])
     T["track_vel_hard"] = (np.exp(-le * 10) + np.exp(-ae * 10)) / 2 - f32(0.2) * (le + ae)
     T["tracking_ang_vel"] = np.exp(-np.square(cmd[:, 2] - bav[:, 2]) * f32(P.tracking_sigma))
     T["tracking_lin_vel"] = np.exp(-np.sum(np.square(cmd[:, :2] - blv[:, :2]), 1) * f32(P.tracking_sigma))
     T["vel_mismatch_exp"] = (np.exp(-np.square(blv[:, 2]) * 10) + np.exp(-np.linalg.norm(bav[:, :2], axis=1) * 5.0)) / 2
-    return {k: np.asarray(v, dtype=f32) for k, v in T.items()}
+    return {k: np.asarray(v, dtype=dtype) for k, v in T.items()}
 
 
-def total_reward(terms, scales, sums, P):
-    """compute_reward (humanoid_env.py:889-907): alphabetical sum, episode sums, clip >= 0."""
-    rew = np.zeros_like(next(iter(terms.values())))
+def total_reward(terms, scales, sums, P, dtype=f32):
+    """compute_reward (humanoid_env.py:889-907): alphabetical sum, episode sums, clip >= 0.
+    dtype as in rewards(); the scales keep their float32 values."""
+    rew = np.zeros_like(next(iter(terms.values())), dtype=dtype)
     for name in sorted(scales):
-        r = (terms[name] * f32(scales[name])).astype(f32)
+        r = (terms[name].astype(dtype) * dtype(f32(scales[name]))).astype(dtype)
         rew = rew + r
         sums[name] = sums[name] + r
     if P.only_positive_rewards:
         rew = np.maximum(rew, 0)
-    return rew.astype(f32)
+    return rew.astype(dtype)
 
 
 def obs_frames(S, L: Layout, P, noise=None):
