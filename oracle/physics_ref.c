@@ -190,21 +190,30 @@ static void load_model(const hg_model* hm, Model* m) {
 
 /* ---------------------------------------------------------------- terrain */
 /* plane z = 0, or the triangulated heightfield (row index = x, column = y, origin at -border) */
-static void ground(const hg_cfg* cfg, const int16_t* hf, real x, real y, real* h, real* n) {
+/* *code (detection report, see Contact.code): DC_UPPER the upper triangle (u < v), DC_ILO / DC_IHI /
+ * DC_JLO / DC_JHI the cell index clamped at that border, DC_UV u or v clamped into [0, 1];
+ * aux (the quantities those decisions compare): u - v after the clamps, and the position in the
+ * unclamped cell, fx - floor(fx) and fy - floor(fy) */
+enum { DC_UPPER = 1, DC_ILO = 2, DC_IHI = 4, DC_JLO = 8, DC_JHI = 16, DC_UV = 32 };
+static void ground(const hg_cfg* cfg, const int16_t* hf, real x, real y, real* h, real* n, int* code, real* aux) {
+  *code = 0;
   if (cfg->terrain_type == 0 || hf == NULL) { *h = 0; n[0] = 0; n[1] = 0; n[2] = 1; return; }
   real hs = cfg->hf_horizontal_scale, vs = cfg->hf_vertical_scale;
   real fx = (x + cfg->hf_border) / hs, fy = (y + cfg->hf_border) / hs;
   int i = (int)floor(fx), j = (int)floor(fy);
-  if (i < 0) i = 0; if (j < 0) j = 0;
-  if (i > cfg->hf_rows - 2) i = cfg->hf_rows - 2; if (j > cfg->hf_cols - 2) j = cfg->hf_cols - 2;
+  if (i < 0) { i = 0; *code |= DC_ILO; } if (j < 0) { j = 0; *code |= DC_JLO; }
+  if (i > cfg->hf_rows - 2) { i = cfg->hf_rows - 2; *code |= DC_IHI; } if (j > cfg->hf_cols - 2) { j = cfg->hf_cols - 2; *code |= DC_JHI; }
   real u = fx - i, v = fy - j;
+  if (u < 0 || u > 1 || v < 0 || v > 1) *code |= DC_UV;
+  aux[1] = fx - floor(fx); aux[2] = fy - floor(fy);
   if (u < 0) u = 0; if (u > 1) u = 1; if (v < 0) v = 0; if (v > 1) v = 1;
   real h00 = vs * hf[i * cfg->hf_cols + j], h10 = vs * hf[(i + 1) * cfg->hf_cols + j];
   real h01 = vs * hf[i * cfg->hf_cols + j + 1], h11 = vs * hf[(i + 1) * cfg->hf_cols + j + 1];
   real dhdx, dhdy;
+  aux[0] = u - v;
   // cells split along the (i,j)-(i+1,j+1) diagonal, as convert_heightfield_to_trimesh tessellates
   if (u >= v) { *h = h00 + u * (h10 - h00) + v * (h11 - h10); dhdx = (h10 - h00) / hs; dhdy = (h11 - h10) / hs; }
-  else { *h = h00 + v * (h01 - h00) + u * (h11 - h01); dhdx = (h11 - h01) / hs; dhdy = (h01 - h00) / hs; }
+  else { *code |= DC_UPPER; *h = h00 + v * (h01 - h00) + u * (h11 - h01); dhdx = (h11 - h01) / hs; dhdy = (h01 - h00) / hs; }
   real inv = 1 / sqrt(dhdx * dhdx + dhdy * dhdy + 1);
   n[0] = -dhdx * inv; n[1] = -dhdy * inv; n[2] = inv;
 }
@@ -399,17 +408,25 @@ static void add_point_jac(const Model* m, const Kin* k, int b, const real* x, co
 static real clamp01(real x) { return x < 0 ? 0 : (x > 1 ? 1 : x); }
 
 /* closest points of segments [p1,q1], [p2,q2] (Ericson, Real-Time Collision Detection 5.1.9) */
-static void seg_seg(const real* p1, const real* q1, const real* p2, const real* q2, real* c1, real* c2) {
+/* returns the case taken: DS_PARALLEL the near-parallel s = 0, DS_TLO t < 0, DS_THI t > 1; aux (the
+ * quantities those decisions compare): denom / (a e), t before its clamp, and s before its last
+ * clamp (0.5 where no clamp ran: the parallel case with t inside) */
+enum { DS_PARALLEL = 1, DS_TLO = 2, DS_THI = 4, DS_COINCIDENT = 8, DS_BOX = 256, DS_BOX_END1 = 1, DS_BOX_INSIDE = 2 };
+static int seg_seg(const real* p1, const real* q1, const real* p2, const real* q2, real* c1, real* c2, real* aux) {
   real d1[3], d2[3], r[3];
   for (int i = 0; i < 3; i++) { d1[i] = q1[i] - p1[i]; d2[i] = q2[i] - p2[i]; r[i] = p1[i] - p2[i]; }
   const real a = v3_dot(d1, d1), e = v3_dot(d2, d2), f = v3_dot(d2, r);
   const real c = v3_dot(d1, r), b = v3_dot(d1, d2);
   const real denom = a * e - b * b;
+  int code = denom > R(1e-6) * a * e ? 0 : DS_PARALLEL;
   real s = denom > R(1e-6) * a * e ? clamp01(QDIV(b * f - c * e, denom)) : 0;
   real t = QDIV(b * s + f, e);
-  if (t < 0) { t = 0; s = clamp01(QDIV(-c, a)); }
-  else if (t > 1) { t = 1; s = clamp01(QDIV(b - c, a)); }
+  aux[0] = denom / (a * e); aux[1] = t; aux[2] = code ? R(0.5) : QDIV(b * f - c * e, denom);
+  if (t < 0) { aux[2] = QDIV(-c, a); } else if (t > 1) { aux[2] = QDIV(b - c, a); }
+  if (t < 0) { t = 0; s = clamp01(QDIV(-c, a)); code |= DS_TLO; }
+  else if (t > 1) { t = 1; s = clamp01(QDIV(b - c, a)); code |= DS_THI; }
   for (int i = 0; i < 3; i++) { c1[i] = p1[i] + d1[i] * s; c2[i] = p2[i] + d2[i] * t; }
+  return code;
 }
 
 /* tangent basis of a contact normal n (reference axis x, or y when n is close to x) */
@@ -439,8 +456,92 @@ static void msolve(const real* L, int off, int n, real* x) {
 /* contact candidate: ground point/sphere c, or capsule pair p */
 typedef struct {
   int active, lam_base, bpos, bneg;
+  real aux[3];  /* the quantities those branches compare (see ground(), seg_seg(), the box face) */
+  int code;  /* the branch detection took (ref_detect): DC_* of ground(), DS_* of seg_seg(), or
+                DS_BOX | DS_BOX_END1 (end sphere 1 chosen) | DS_BOX_INSIDE for the base-box face */
   real phi, n[3], xpos[3], xneg[3], mu;
 } Contact;
+
+/* contact detection at the pose of `k`, in priority order; returns the number of candidates */
+static int detect(const hg_cfg* cfg, const Model* m, const int16_t* hf, const Kin* k, const real* root,
+                  int fixed, real fric, Contact* cand) {
+  const real off_c = cfg->contact_offset;
+  int ncand = 0;
+  for (int item = 0; item < m->nc + m->npair; item++) {
+    /* items: ground candidates [0, nleg), pairs, ground candidates [nleg, nc) */
+    Contact* ct = &cand[ncand++];
+    memset(ct, 0, sizeof(*ct));
+    const int is_pair = item >= m->nleg && item < m->nleg + m->npair;
+    if (!is_pair) {
+      const int c = item < m->nleg ? item : item - m->npair;
+      const int b = m->cbody[c];
+      real x[3];
+      mat3_vec(k->Rb[b], m->cpos[c], x);
+      for (int i = 0; i < 3; i++) x[i] += k->o[b][i];
+      real hg, nrm[3];
+      ground(cfg, hf, x[0] + root[0], x[1] + root[1], &hg, nrm, &ct->code, ct->aux);
+      const real r = m->crad[c];
+      ct->phi = (x[2] + root[2] - hg) * nrm[2] - r;
+      for (int i = 0; i < 3; i++) { ct->n[i] = nrm[i]; ct->xpos[i] = x[i] - r * nrm[i]; }
+      ct->bpos = b; ct->bneg = -1;
+      ct->mu = R(0.5) * (fric + cfg->ground_friction);
+      ct->lam_base = 3 * c;
+      ct->active = !fixed && ct->phi < off_c;
+    } else {
+      const int p = item - m->nleg;
+      const int ca = m->pair[p][0], cb = m->pair[p][1];
+      const int ba = m->capbody[ca], bb = m->capbody[cb];
+      real a0[3], a1[3], b0[3], b1[3], pa[3], pb[3], dv[3];
+      mat3_vec(k->Rb[ba], m->cap0[ca], a0); mat3_vec(k->Rb[ba], m->cap1[ca], a1);
+      mat3_vec(k->Rb[bb], m->cap0[cb], b0); mat3_vec(k->Rb[bb], m->cap1[cb], b1);
+      for (int i = 0; i < 3; i++) { a0[i] += k->o[ba][i]; a1[i] += k->o[ba][i]; b0[i] += k->o[bb][i]; b1[i] += k->o[bb][i]; }
+      const real rb = m->caprad[cb];
+      real ra = m->caprad[ca], dist;
+      if (m->capkind[ca] == 1) {
+        /* base-box bottom face (base frame: z = cap0.z over [cap0.x, cap1.x] x [cap0.y, cap1.y],
+           outward normal -z) vs the end sphere of capsule cb that lies closer to it */
+        const real* R0 = k->Rb[0];
+        real h[2], xy[2][2];
+        const real* ends[2] = {b0, b1};
+        for (int s = 0; s < 2; s++) {  /* end sphere in the base frame: R0^T x */
+          const real* x = ends[s];
+          xy[s][0] = R0[0] * x[0] + R0[3] * x[1] + R0[6] * x[2];
+          xy[s][1] = R0[1] * x[0] + R0[4] * x[1] + R0[7] * x[2];
+          h[s] = m->cap0[ca][2] - (R0[2] * x[0] + R0[5] * x[1] + R0[8] * x[2]);  /* depth below the face */
+        }
+        const int s = h[1] < h[0] ? 1 : 0;
+        const int inside = xy[s][0] >= m->cap0[ca][0] && xy[s][0] <= m->cap1[ca][0] &&
+                           xy[s][1] >= m->cap0[ca][1] && xy[s][1] <= m->cap1[ca][1];
+        for (int i = 0; i < 3; i++) {
+          ct->n[i] = -R0[i * 3 + 2];
+          pb[i] = ends[s][i];
+          pa[i] = ends[s][i] - h[s] * ct->n[i];
+        }
+        ra = 0;
+        dist = inside ? h[s] : R(1e3);
+        ct->code = DS_BOX | (s ? DS_BOX_END1 : 0) | (inside ? DS_BOX_INSIDE : 0);
+        /* aux: h1 - h0, the chosen end's least signed distance inside the rectangle, its depth */
+        ct->aux[0] = h[1] - h[0];
+        ct->aux[1] = fmin(fmin(xy[s][0] - m->cap0[ca][0], m->cap1[ca][0] - xy[s][0]),
+                          fmin(xy[s][1] - m->cap0[ca][1], m->cap1[ca][1] - xy[s][1]));
+        ct->aux[2] = h[s];
+      } else {
+        ct->code = seg_seg(a0, a1, b0, b1, pa, pb, ct->aux);
+        for (int i = 0; i < 3; i++) dv[i] = pb[i] - pa[i];
+        dist = sqrt(v3_dot(dv, dv));
+        if (dist > R(1e-9)) for (int i = 0; i < 3; i++) ct->n[i] = QDIV(dv[i], dist);
+        else { ct->n[0] = 0; ct->n[1] = -1; ct->n[2] = 0; ct->code |= DS_COINCIDENT; }  /* left -> right is -y in the base frame */
+      }
+      ct->phi = dist - ra - rb;
+      for (int i = 0; i < 3; i++) { ct->xpos[i] = pb[i] - rb * ct->n[i]; ct->xneg[i] = pa[i] + ra * ct->n[i]; }
+      ct->bpos = bb; ct->bneg = ba;
+      ct->mu = fric;
+      ct->lam_base = LAM_PAIR + 3 * p;
+      ct->active = ct->phi < off_c;
+    }
+  }
+  return ncand;
+}
 
 static void substep(const hg_cfg* cfg, const Model* m, const int16_t* hf, real* root, real* q,
                     real* qd, real* lamst, const real* act, real* tau, real mass0, real fric, real* cf_out,
@@ -478,76 +579,9 @@ static void substep(const hg_cfg* cfg, const Model* m, const int16_t* hf, real* 
   for (int i = 0; i < NV; i++) nu[i] += dt * acc[i];
 
   /* ---- contact detection, in priority order ---- */
-  const real beta = cfg->baumgarte, vmax = cfg->max_depenetration_vel, off_c = cfg->contact_offset;
+  const real beta = cfg->baumgarte, vmax = cfg->max_depenetration_vel;
   Contact cand[NC_MAX + NP_MAX];
-  int ncand = 0;
-  for (int item = 0; item < m->nc + m->npair; item++) {
-    /* items: ground candidates [0, nleg), pairs, ground candidates [nleg, nc) */
-    Contact* ct = &cand[ncand++];
-    memset(ct, 0, sizeof(*ct));
-    const int is_pair = item >= m->nleg && item < m->nleg + m->npair;
-    if (!is_pair) {
-      const int c = item < m->nleg ? item : item - m->npair;
-      const int b = m->cbody[c];
-      real x[3];
-      mat3_vec(k.Rb[b], m->cpos[c], x);
-      for (int i = 0; i < 3; i++) x[i] += k.o[b][i];
-      real hg, nrm[3];
-      ground(cfg, hf, x[0] + root[0], x[1] + root[1], &hg, nrm);
-      const real r = m->crad[c];
-      ct->phi = (x[2] + root[2] - hg) * nrm[2] - r;
-      for (int i = 0; i < 3; i++) { ct->n[i] = nrm[i]; ct->xpos[i] = x[i] - r * nrm[i]; }
-      ct->bpos = b; ct->bneg = -1;
-      ct->mu = R(0.5) * (fric + cfg->ground_friction);
-      ct->lam_base = 3 * c;
-      ct->active = !fixed && ct->phi < off_c;
-    } else {
-      const int p = item - m->nleg;
-      const int ca = m->pair[p][0], cb = m->pair[p][1];
-      const int ba = m->capbody[ca], bb = m->capbody[cb];
-      real a0[3], a1[3], b0[3], b1[3], pa[3], pb[3], dv[3];
-      mat3_vec(k.Rb[ba], m->cap0[ca], a0); mat3_vec(k.Rb[ba], m->cap1[ca], a1);
-      mat3_vec(k.Rb[bb], m->cap0[cb], b0); mat3_vec(k.Rb[bb], m->cap1[cb], b1);
-      for (int i = 0; i < 3; i++) { a0[i] += k.o[ba][i]; a1[i] += k.o[ba][i]; b0[i] += k.o[bb][i]; b1[i] += k.o[bb][i]; }
-      const real rb = m->caprad[cb];
-      real ra = m->caprad[ca], dist;
-      if (m->capkind[ca] == 1) {
-        /* base-box bottom face (base frame: z = cap0.z over [cap0.x, cap1.x] x [cap0.y, cap1.y],
-           outward normal -z) vs the end sphere of capsule cb that lies closer to it */
-        const real* R0 = k.Rb[0];
-        real h[2], xy[2][2];
-        const real* ends[2] = {b0, b1};
-        for (int s = 0; s < 2; s++) {  /* end sphere in the base frame: R0^T x */
-          const real* x = ends[s];
-          xy[s][0] = R0[0] * x[0] + R0[3] * x[1] + R0[6] * x[2];
-          xy[s][1] = R0[1] * x[0] + R0[4] * x[1] + R0[7] * x[2];
-          h[s] = m->cap0[ca][2] - (R0[2] * x[0] + R0[5] * x[1] + R0[8] * x[2]);  /* depth below the face */
-        }
-        const int s = h[1] < h[0] ? 1 : 0;
-        const int inside = xy[s][0] >= m->cap0[ca][0] && xy[s][0] <= m->cap1[ca][0] &&
-                           xy[s][1] >= m->cap0[ca][1] && xy[s][1] <= m->cap1[ca][1];
-        for (int i = 0; i < 3; i++) {
-          ct->n[i] = -R0[i * 3 + 2];
-          pb[i] = ends[s][i];
-          pa[i] = ends[s][i] - h[s] * ct->n[i];
-        }
-        ra = 0;
-        dist = inside ? h[s] : R(1e3);
-      } else {
-        seg_seg(a0, a1, b0, b1, pa, pb);
-        for (int i = 0; i < 3; i++) dv[i] = pb[i] - pa[i];
-        dist = sqrt(v3_dot(dv, dv));
-        if (dist > R(1e-9)) for (int i = 0; i < 3; i++) ct->n[i] = QDIV(dv[i], dist);
-        else { ct->n[0] = 0; ct->n[1] = -1; ct->n[2] = 0; }  /* left -> right is -y in the base frame */
-      }
-      ct->phi = dist - ra - rb;
-      for (int i = 0; i < 3; i++) { ct->xpos[i] = pb[i] - rb * ct->n[i]; ct->xneg[i] = pa[i] + ra * ct->n[i]; }
-      ct->bpos = bb; ct->bneg = ba;
-      ct->mu = fric;
-      ct->lam_base = LAM_PAIR + 3 * p;
-      ct->active = ct->phi < off_c;
-    }
-  }
+  const int ncand = detect(cfg, m, hf, &k, root, fixed, fric, cand);
   /* ---- rows: contacts (<= MAX_CONTACT_POINTS), joint limits, joint friction; the rest dropped ---- */
   static __thread Row rows[MAX_ROWS];
   int nr = 0, npts = 0;
@@ -758,6 +792,34 @@ int API(ref_dynamics)(const hg_model* hm, const real* root, const real* q, const
 }
 
 int API(ref_lamw)(void) { return LAMW; }
+
+/* The detection of the NEXT substep of n states, without stepping: per item (priority order:
+ * ground candidates [0, nleg), the pairs, ground candidates [nleg, nc); HG_MAX_CONTACTS +
+ * HG_MAX_PAIRS columns, the unused ones zero) the gap phi, the active flag, the normal and the
+ * branch code (Contact.code) with the three compared quantities (Contact.aux) — the same detect()
+ * the substep calls.  For tests that must know
+ * which branch a planted state takes (oracle/step_cases.py). */
+int API(ref_detect)(const hg_cfg* cfg, const hg_model* hm, const int16_t* hf, int n, const real* root,
+                    const real* q, const real* mass0, real* phi, int32_t* active, real* normal, int32_t* code, real* aux) {
+  Model m;
+  load_model(hm, &m);
+  const int W = NC_MAX + NP_MAX;
+  for (int e = 0; e < n; e++) {
+    real nu[NV] = {0};
+    Kin k;
+    kinematics(&m, root + (size_t)e * 13 + 3, q + (size_t)e * ND, nu, mass0[e], &k);
+    Contact cand[NC_MAX + NP_MAX];
+    const int nc = detect(cfg, &m, hf, &k, root + (size_t)e * 13, cfg->fix_base_link, R(1), cand);
+    for (int i = 0; i < W; i++) {
+      const size_t o = (size_t)e * W + i;
+      phi[o] = i < nc ? cand[i].phi : 0;
+      active[o] = i < nc ? cand[i].active : 0;
+      code[o] = i < nc ? cand[i].code : 0;
+      for (int d = 0; d < 3; d++) { normal[o * 3 + d] = i < nc ? cand[i].n[d] : 0; aux[o * 3 + d] = i < nc ? cand[i].aux[d] : 0; }
+    }
+  }
+  return 0;
+}
 
 /* host threads of the OpenMP env loop (bench.py cpu_baseline: all cores, then one core) */
 #ifndef REF_FLOAT

@@ -39,10 +39,11 @@ def set_threads(n):
 class RefSim:
     """AoS CPU simulator state for n envs (root[n,13], q/qd[n,12], warm-start lambdas)."""
 
-    def __init__(self, cfg, model, n, precision="f64", heightfield=None):
+    def __init__(self, cfg, model, n, precision="f64", heightfield=None, library=None):
+        """library: another build of physics_ref.c to step with (tests' wrong variants)."""
         self.cfg, self.model, self.n = cfg, model, n
         self.dt = np.float64 if precision == "f64" else np.float32
-        self.fn = getattr(lib(), "ref_step_" + precision)
+        self.fn = getattr(library or lib(), "ref_step_" + precision)
         self.lamw = lib().ref_lamw_f64()
         self.root = np.zeros((n, 13), self.dt)
         self.root[:, 6] = 1.0
@@ -67,6 +68,32 @@ class RefSim:
                 _p(self.contact), _p(self.rigid), _p(self.nonfinite), _p(self.dropped))
 
 
+def detect(cfg, model, root, q, mass0=None, precision="f64", heightfield=None):
+    """The contact detection the next substep of n states (root[n, 13], q[n, 12]) will run
+    (physics_ref.c ref_detect), per item in priority order (ground candidates [0, nleg), the pairs,
+    ground candidates [nleg, nc); 40 columns, unused ones zero): dict of phi[n, 40], active[n, 40],
+    normal[n, 40, 3], code[n, 40] (the DC_* / DS_* branch codes) and aux[n, 40, 3] (the quantities
+    those branches compare)."""
+    dt = np.float64 if precision == "f64" else np.float32
+    root = np.ascontiguousarray(np.atleast_2d(root), dt)
+    n = root.shape[0]
+    q = np.ascontiguousarray(np.broadcast_to(q, (n, 12)), dt)
+    m0 = np.ascontiguousarray(np.broadcast_to(model.mass[0] if mass0 is None else mass0, (n,)), dt)
+    W = len(model.contact_body) + len(model.pair)
+    out = dict(phi=np.zeros((n, W), dt), active=np.zeros((n, W), np.int32), normal=np.zeros((n, W, 3), dt),
+               code=np.zeros((n, W), np.int32), aux=np.zeros((n, W, 3), dt))
+    hf = None if heightfield is None else _p(np.ascontiguousarray(heightfield, np.int16))
+    getattr(lib(), "ref_detect_" + precision)(ctypes.byref(cfg), ctypes.byref(model), hf, ctypes.c_int(n), _p(root), _p(q),
+                                              _p(m0), _p(out["phi"]), _p(out["active"]), _p(out["normal"]),
+                                              _p(out["code"]), _p(out["aux"]))
+    return out
+
+
+# branch codes of detect() (physics_ref.c DC_* / DS_*)
+DC_UPPER, DC_ILO, DC_IHI, DC_JLO, DC_JHI, DC_UV = 1, 2, 4, 8, 16, 32
+DS_PARALLEL, DS_TLO, DS_THI, DS_COINCIDENT, DS_BOX, DS_BOX_END1, DS_BOX_INSIDE = 1, 2, 4, 8, 256, 1, 2
+
+
 def rigid_states(model, root, q, qd, mass0=None, precision="f64"):
     """[n, 13, 13] body states (position, quaternion xyzw, linear / angular velocity, world frame)
     of n states, by the oracle's own forward kinematics (physics_ref.c rigid_states), no step."""
@@ -85,7 +112,7 @@ def rigid_states(model, root, q, qd, mass0=None, precision="f64"):
 def ground(cfg, hf, x, y):
     """(height, unit normal[..., 3]) of the terrain under world points (x, y), numpy float64: the
     plane z = 0, or the int16 heightfield triangulated along the (i, j)-(i+1, j+1) diagonal —
-    physics_ref.c:179-196 (`ground`) element for element.  For tests that classify contacts by
+    physics_ref.c `ground` element for element.  For tests that classify contacts by
     the triangle they sit on."""
     x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
     if cfg.terrain_type == 0 or hf is None:
@@ -118,7 +145,7 @@ def quat_rotate(q, v):
 def ground_candidates(model, rigid):
     """World centres [n, nc, 3] of the model's ground-contact spheres from rigid states
     [n, bodies, 13] (position, quaternion xyzw, ...): x = o_b + R_b cpos_c, the point whose
-    (x, y) physics_ref.c:472-477 looks the terrain up under."""
+    (x, y) physics_ref.c `detect` looks the terrain up under."""
     nc = len(model.contact_body)
     cb = np.array([model.contact_body[c] for c in range(nc)])
     cp = np.array([list(model.contact_pos[c]) for c in range(nc)], np.float64)
