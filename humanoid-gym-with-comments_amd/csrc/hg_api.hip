@@ -1,5 +1,6 @@
 // hg_api.hip — host side of the hg_sim C ABI (include/hgsim.h): arena layout, tensor
 // descriptors, launches.  No host synchronisation on any step/post path.
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -16,6 +17,8 @@ extern "C" int hg_launch_post(const HgState* S, const hg_cfg* hcfg, uint64_t cou
                               int ep_slot, HgSink sink, HgCurriculum cur, hipStream_t stream);
 extern "C" int hg_launch_actuator_draw(const HgState* S, uint64_t counter, int mode, const uint8_t* mask,
                                        hipStream_t stream);
+extern "C" int hg_launch_depth(const HgState* S, const hg_cfg* hcfg, const hg_depth_cam* cam, const float* pitch,
+                               float* out, int64_t env_stride, uint64_t counter, int mapping, hipStream_t stream);
 
 namespace {
 
@@ -559,6 +562,30 @@ extern "C" int hg_measure_heights(void* sim, const float* points_xy, int num_poi
   hipLaunchKernelGGL(k_heights, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s->S,
                      points_xy, num_points, out);
   return hipGetLastError() == hipSuccess ? HG_OK : fail(s, HG_ERR_HIP, "k_heights launch failed");
+}
+
+// ---- depth camera (hg_depth.hip): argument checks here, nothing is launched on a refusal
+extern "C" int hg_render_depth(void* sim, const hg_depth_cam* cam, const float* pitch, float* out, int64_t env_stride,
+                               uint64_t counter, void* stream) {
+  Sim* s = (Sim*)sim;
+  if (!s || !cam || !out) return fail(s, HG_ERR_ARG, "hg_render_depth: null argument");
+  if (cam->width <= 0 || cam->height <= 0) return fail(s, HG_ERR_ARG, "hg_render_depth: width and height must be > 0");
+  if ((int64_t)cam->width * cam->height > 262144)
+    return fail(s, HG_ERR_ARG, "hg_render_depth: more than 262144 pixels (the noise draw's 16-bit block index)");
+  if (env_stride < (int64_t)cam->width * cam->height)
+    return fail(s, HG_ERR_ARG, "hg_render_depth: env_stride below width * height");
+  if (!(cam->near_clip >= 0.f) || !(cam->far_clip > cam->near_clip) || !(cam->far_clip < INFINITY))
+    return fail(s, HG_ERR_ARG, "hg_render_depth: need 0 <= near_clip < far_clip < inf");
+  if (!(cam->horizontal_fov_deg > 0.f) || !(cam->horizontal_fov_deg < 180.f))
+    return fail(s, HG_ERR_ARG, "hg_render_depth: horizontal_fov_deg must be inside (0, 180)");
+  if (!(cam->noise >= 0.f)) return fail(s, HG_ERR_ARG, "hg_render_depth: noise must be >= 0");
+  // pixel-to-lane mapping: 8 x 8 tiles per wave unless HG_DEPTH_MAP=rows (64 row-major pixels per
+  // wave; kept for the timing comparison of scripts/depth_timing.py)
+  const char* m = getenv("HG_DEPTH_MAP");
+  const int mapping = (m && strcmp(m, "rows") == 0) ? 1 : 0;
+  if (hg_launch_depth(&s->S, &s->cfg, cam, pitch, out, env_stride, counter, mapping, (hipStream_t)stream) != 0)
+    return fail(s, HG_ERR_HIP, "k_depth launch failed");
+  return HG_OK;
 }
 
 __global__ void k_set_root_all(HgState S, const float* root) {

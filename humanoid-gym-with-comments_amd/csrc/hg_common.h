@@ -145,6 +145,7 @@ enum HgRngPurpose : uint32_t {
   RNG_ACT_DELAY = 1, RNG_ACT_NOISE = 2, RNG_OBS_NOISE = 3, RNG_CMD = 4, RNG_PUSH = 5,
   RNG_RESET_DOF = 6, RNG_RESET_ROOT = 7, RNG_TERRAIN = 8,
   RNG_ACTUATOR = 10,  // 9 is the rollout's action sample (hg_rollout.hip)
+  RNG_DEPTH_NOISE = 11,  // hg_render_depth's per-pixel noise (hg_depth.hip)
 };
 
 // uniform in [0,1): 24 high bits

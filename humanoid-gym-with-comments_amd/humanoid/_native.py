@@ -87,6 +87,47 @@ class HgDesc(ctypes.Structure):
                 ("shape", ctypes.c_int64 * 4), ("strides", ctypes.c_int64 * 4)]
 
 
+class HgDepthCam(ctypes.Structure):
+    """hg_depth_cam (include/hgsim.h): the pinhole depth camera hg_render_depth renders."""
+    _fields_ = [("width", i32), ("height", i32), ("horizontal_fov_deg", f32), ("pos", f32 * 3),
+                ("near_clip", f32), ("far_clip", f32), ("normalize", i32), ("noise", f32)]
+
+
+DEPTH_MAX_PIXELS = 262144  # hg_render_depth: W * H bound (the noise draw's 16-bit Philox block index)
+
+
+def depth_cam(depth_cfg, normalize=None, noise=None, env_stride=None):
+    """HgDepthCam from a config's ``depth`` class (XBotLCfg.depth).  normalize / noise override the
+    config's ``normalize`` / ``dis_noise``.  Raises ValueError on everything hg_render_depth would
+    refuse (include/hgsim.h), so a bad config fails before any launch; env_stride, when given, is
+    checked against W * H as well."""
+    w, h = (int(v) for v in depth_cfg.original)
+    cam = HgDepthCam()
+    cam.width, cam.height = w, h
+    cam.horizontal_fov_deg = float(depth_cfg.horizontal_fov)
+    pos = [float(v) for v in depth_cfg.position]
+    if len(pos) != 3:
+        raise ValueError(f"depth.position must have 3 entries, got {len(pos)}")
+    for k in range(3):
+        cam.pos[k] = pos[k]
+    cam.near_clip, cam.far_clip = float(depth_cfg.near_clip), float(depth_cfg.far_clip)
+    cam.normalize = int(bool(depth_cfg.normalize if normalize is None else normalize))
+    cam.noise = float(depth_cfg.dis_noise if noise is None else noise)
+    if w <= 0 or h <= 0:
+        raise ValueError(f"depth.original must be positive (W, H), got {(w, h)}")
+    if w * h > DEPTH_MAX_PIXELS:
+        raise ValueError(f"depth.original: {w} x {h} pixels exceed {DEPTH_MAX_PIXELS}")
+    if env_stride is not None and env_stride < w * h:
+        raise ValueError(f"depth: env stride {env_stride} below W * H = {w * h}")
+    if not (0.0 <= cam.near_clip < cam.far_clip < float("inf")):
+        raise ValueError(f"depth: need 0 <= near_clip < far_clip < inf, got {cam.near_clip}, {cam.far_clip}")
+    if not (0.0 < cam.horizontal_fov_deg < 180.0):
+        raise ValueError(f"depth.horizontal_fov must be inside (0, 180), got {cam.horizontal_fov_deg}")
+    if not (cam.noise >= 0.0):
+        raise ValueError(f"depth noise must be >= 0, got {cam.noise}")
+    return cam
+
+
 # tensor ids (enum hg_tensor_id)
 TENSOR_IDS = [
     "ROOT_STATE", "DOF_POS", "DOF_VEL", "CONTACT_FORCES", "RIGID_STATE", "TORQUES", "ACTIONS",
@@ -106,7 +147,7 @@ EXPORTS = ["hg_arena_bytes", "hg_create", "hg_destroy", "hg_last_error", "hg_ten
            "hg_post", "hg_set_rollout_sink", "hg_ep_stats_slot", "hg_obs_head", "hg_obs_window_advance", "hg_update_cfg", "hg_reset_masked",
            "hg_set_command_range_x", "hg_publish_terrain_level", "hg_set_dof_state_indexed", "hg_set_root_state_indexed",
            "hg_set_root_state", "hg_set_env_props", "hg_set_actuator_props",
-           "hg_measure_heights", "hg_gae_scan", "hg_gae_stats_len", "hg_gae_normalize", "hg_adam_step", "hg_adam_chunk", "hg_kl_mean", "hg_kl_lr_rule",
+           "hg_measure_heights", "hg_render_depth", "hg_gae_scan", "hg_gae_stats_len", "hg_gae_normalize", "hg_adam_step", "hg_adam_chunk", "hg_kl_mean", "hg_kl_lr_rule",
            "hg_rollout_act", "hg_rollout_act_head", "hg_rollout_act_tail", "hg_rollout_env", "hg_gather_rows", "hg_gather_rows_ex", "hg_gather_stacked", "hg_ppo_loss", "hg_ppo_loss_lr", "hg_ppo_loss_scratch", "hg_ppo_loss_backward",
            "hg_mirror_rows", "hg_sym_loss", "hg_sym_loss_scratch", "hg_sym_loss_backward",
            "hg_mlp_act_backward", "hg_mlp_act_backward_scratch", "hg_colsum_jobs", "hg_linear_skinny_supported",
@@ -194,6 +235,8 @@ def load_library(path=LIB_PATH):
     L.hg_set_root_state_indexed.argtypes = [vp, vp, ctypes.c_int, vp, vp]
     L.hg_measure_heights.restype = ctypes.c_int
     L.hg_measure_heights.argtypes = [vp, vp, ctypes.c_int, vp, vp]
+    L.hg_render_depth.restype = ctypes.c_int
+    L.hg_render_depth.argtypes = [vp, ctypes.POINTER(HgDepthCam), vp, vp, ctypes.c_int64, ctypes.c_uint64, vp]
     L.hg_set_root_state.restype = ctypes.c_int
     L.hg_set_root_state.argtypes = [vp, vp, vp]
     L.hg_set_env_props.restype = ctypes.c_int

@@ -95,6 +95,23 @@ class XBotLCfg(BaseConfig):
         restitution = 0.0
         slope_treshold = 0.75
 
+    class depth:
+        # base-mounted forward depth camera (attach_camera, humanoid_env.py:399-423 of the
+        # reference reads use_camera, original, horizontal_fov, position, angle; it ships no
+        # values, so all of these are BUILD-DEFINED).  Rendered by hg_render_depth: rays marched
+        # against the terrain K_step collides with; the robot's own links are not drawn.
+        use_camera = False
+        original = (106, 60)              # (W, H) pixels
+        horizontal_fov = 87               # degrees
+        position = [0.10, 0.0, 0.15]      # in the base frame
+        angle = [20, 30]                  # camera pitch range, degrees, positive = down, drawn per env
+        near_clip = 0.0                   # metres, planar depth
+        far_clip = 3.0
+        update_interval = 5               # env steps between renders
+        buffer_len = 2                    # frames kept per env (env.depth_buffer)
+        dis_noise = 0.0                   # uniform +- metres added before the clip
+        normalize = True                  # (d - near) / (far - near) - 0.5
+
     class noise:
         add_noise = True
         noise_level = 0.6

@@ -15,6 +15,10 @@ gymtorch-wrapped tensors (``root_states[:, 3:7]``, ``dof_pos[env_ids] = ...``).
 changes the privileged frame's width mid-run) widens every privileged frame by the measured
 terrain heights under the sample grid, written on the device by the post launch's window kernel;
 ``num_privileged_obs`` then is ``c_frame_stack * (73 + P)`` here and on ``cfg.env``.
+
+``depth.use_camera`` (the reference's attach_camera, humanoid_env.py:399-423; values BUILD-DEFINED)
+adds a base-mounted depth camera rendered by hg_render_depth every ``depth.update_interval`` steps
+into the ring ``depth_buffer``; off (the default) nothing of it exists.
 """
 import ctypes
 
@@ -196,6 +200,11 @@ class XBotLFreeEnv(BaseTask):
         self.init_done = True
         # reset_idx(all) + compute_observations() (humanoid_env.py:176-178)
         self._launch_reset(None)
+        if self._depth is not None:
+            # the first frame, from the creation-time pose, in every ring slot
+            self._render_depth_slot()
+            for k in range(1, self._depth_len):
+                self.depth_buffer[:, k].copy_(self.depth_buffer[:, 0])
 
     # ------------------------------------------------------------------ config
     def _parse_cfg(self, cfg):
@@ -300,6 +309,74 @@ class XBotLFreeEnv(BaseTask):
             self.cfg.env.num_privileged_obs = self.num_privileged_obs
         self._get_env_origins()
         self._randomize_props()
+        self._init_depth_camera()
+
+    # ------------------------------------------------------------------ depth camera
+    _depth = None  # the cfg's depth class when depth.use_camera is on
+
+    def _init_depth_camera(self):
+        """attach_camera (humanoid_env.py:399-423): a forward depth camera on the base, its pitch
+        drawn per env from depth.angle.  The image is ray-marched against the terrain by
+        hg_render_depth (no graphics pipeline); the robot's own links are not drawn.  Nothing is
+        created unless depth.use_camera is on."""
+        d = getattr(self.cfg, "depth", None)
+        if d is None or not getattr(d, "use_camera", False):
+            return
+        self._depth = d
+        w, h = (int(v) for v in d.original)
+        self._depth_len = int(d.buffer_len)
+        self._depth_interval = int(d.update_interval)
+        if self._depth_len < 1 or self._depth_interval < 1:
+            raise ValueError("depth.buffer_len and depth.update_interval must be >= 1")
+        self._depth_cam = N.depth_cam(d, env_stride=self._depth_len * h * w)  # refuses a bad config here
+        # the pitch of every global env from a creation stream of its own, sliced to this shard
+        off, total = self._global_ids()
+        lo, hi = (float(np.deg2rad(a)) for a in d.angle)
+        u = torch.rand(total, generator=self._creation_generator(4))[off:off + self.num_envs]
+        self.depth_cam_pitch = (lo + (hi - lo) * u).to(self.device, torch.float32).contiguous()
+        # a physical ring: render k writes slot k % buffer_len in place
+        self.depth_buffer = torch.zeros(self.num_envs, self._depth_len, h, w, dtype=torch.float32, device=self.device)
+        self._depth_renders = 0
+        # the public surface exists only with the camera on
+        self.depth_frame = self._depth_frame
+        self.render_depth = self._render_depth
+
+    def _launch_depth(self, cam, out, env_stride, counter):
+        p = self.depth_cam_pitch
+        if p.dtype != torch.float32 or p.shape != (self.num_envs,) or not p.is_contiguous() or p.device != self.device:
+            raise ValueError(f"depth_cam_pitch must stay a contiguous float32 [{self.num_envs}] tensor on {self.device}")
+        N.check(self.hg.hg_render_depth(self.sim, ctypes.byref(cam), ctypes.c_void_p(p.data_ptr()),
+                                        ctypes.c_void_p(out.data_ptr()), ctypes.c_int64(env_stride),
+                                        ctypes.c_uint64(counter), self._stream()), self.sim)
+
+    def _render_depth_slot(self):
+        """One render into the ring's next slot (noise keyed by the step counter)."""
+        slot = self._depth_renders % self._depth_len
+        self._launch_depth(self._depth_cam, self.depth_buffer[:, slot], self.depth_buffer.stride(0),
+                           self.common_step_counter)
+        self._depth_renders += 1
+
+    def _depth_frame(self, age=0):
+        """[N, H, W] view of the frame rendered `age` renders ago (0: the latest).  An env that
+        reset since keeps its pre-reset frames until the next render."""
+        if not 0 <= age < self._depth_len:
+            raise ValueError(f"depth_frame: age must be in [0, {self._depth_len}), got {age}")
+        return self.depth_buffer[:, (self._depth_renders - 1 - age) % self._depth_len]
+
+    def _render_depth(self, out=None, normalize=None, noise=None):
+        """Render the camera now, at the current root states, into a fresh or given contiguous
+        float32 [N, H, W] tensor (the ring is not touched).  normalize / noise override
+        depth.normalize / depth.dis_noise; the noise is keyed by the step counter."""
+        cam = self._depth_cam if normalize is None and noise is None else N.depth_cam(self._depth, normalize, noise)
+        h, w = cam.height, cam.width
+        if out is None:
+            out = torch.empty(self.num_envs, h, w, dtype=torch.float32, device=self.device)
+        elif (out.dtype != torch.float32 or tuple(out.shape) != (self.num_envs, h, w) or not out.is_contiguous()
+              or out.device != self.device):
+            raise ValueError(f"render_depth: out must be a contiguous float32 [{self.num_envs}, {h}, {w}] tensor on "
+                             f"{self.device}")
+        self._launch_depth(cam, out, h * w, self.common_step_counter)
+        return out
 
     def _view(self, tid):
         d = N.HgDesc()
@@ -648,6 +725,19 @@ class XBotLFreeEnv(BaseTask):
         if kt is not None:
             kt.stop("k_post")
         self._publish_extras()
+        if self._depth is not None:
+            # after the post launch: the pose the observations were written from (post-reset).
+            # extras["depth"] is the new frame on render steps, None between them (the convention
+            # of the code attach_camera comes from)
+            if self.common_step_counter % self._depth_interval == 0:
+                if kt is not None:
+                    kt.start("k_depth")
+                self._render_depth_slot()
+                if kt is not None:
+                    kt.stop("k_depth")
+                self.extras["depth"] = self.depth_frame(0)
+            else:
+                self.extras["depth"] = None
         if sink is not None:
             self.extras["rollout_sink"] = sink  # the slot tensors this step's post launch filled
         return self.get_observations(), self.get_privileged_observations(), self.rew_buf, self.reset_buf, self.extras

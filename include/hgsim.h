@@ -334,6 +334,50 @@ int hg_set_actuator_props(void* sim, const float* kp_scale, const float* kd_scal
  * vertical_scale.  Zeros on a plane (terrain_type 0), as the reference. */
 int hg_measure_heights(void* sim, const float* points_xy, int num_points, float* out, void* stream);
 
+/* ---- base-mounted depth camera (replaces the camera sensor attach_camera creates,
+ * humanoid_env.py:399-423, and its depth image; BUILD-DEFINED: there is no graphics pipeline here,
+ * the image is ray-marched against the terrain by a HIP kernel) ----
+ * A standalone call like hg_measure_heights: it reads the root states and the heightfield fields
+ * of the device hg_cfg, writes only `out`, allocates nothing and does not synchronise (capturable).
+ * Camera conventions:
+ *   - the camera frame is x forward, y left, z up;
+ *   - its world rotation is R = R_base(q_xyzw, normalised) * R_y(pitch[e]); positive pitch looks
+ *     down (x turns toward -z); pitch: device f32 [N] radians, NULL = 0;
+ *   - its origin is o = p_base + R_base * pos;
+ *   - row 0 is the top of the image, column 0 its left edge (+y);
+ *   - pixel (r, c) has the camera-frame direction
+ *       d = (1, -(c + 0.5 - W/2) / fx, -(r + 0.5 - H/2) / fx),  fx = (W/2) / tan(fov/2)
+ *     (pinhole, square pixels);
+ *   - the ray parameter t of o + t R d IS the planar depth (Isaac Gym's depth image after the sign
+ *     flip), not the distance along the ray.
+ * Scene: the plane z = 0 when terrain_type == 0 or the heightfield is NULL; otherwise the
+ * heightfield surface with vertices (i hs - border, j hs - border, vs hf[i][j]) and every cell
+ * split along its (i,j)-(i+1,j+1) diagonal — K_step's contact surface, triangle for triangle.
+ * Cells outside [0, rows-2] x [0, cols-2] hold no surface (a ray may enter the extent from
+ * outside).  The surface is two-sided: the result is the first intersection with t >= 0 from either
+ * side, so a camera under the terrain sees it from below.  No intersection within far_clip, or a
+ * non-finite pose / pitch, gives far_clip.  Deviations from a rendered image: the robot's own links
+ * are not drawn, and there are no vertical walls where the reference's trimesh conversion
+ * (slope_treshold) would insert them.
+ * Pixel value: raw = t; + noise * (2 u01(word) - 1) when noise > 0, the Philox draw keyed like
+ * every other (seed; global env id, counter, block = pix >> 2, purpose 11), word pix & 3, pix =
+ * r W + c; clamped to [near_clip, far_clip]; normalize != 0 then maps it to
+ * (d - near) / (far - near) - 0.5.  Element (e, r, c) is out[e * env_stride + r * W + c], so `out`
+ * may be one slot of a [N, slots, H, W] ring (env_stride = slots * H * W).
+ * HG_ERR_ARG before any launch (hg_last_error says which): sim, cam or out NULL; W <= 0 or H <= 0;
+ * W * H > 262144 (the 16-bit Philox block field); env_stride < W * H; far_clip <= near_clip,
+ * near_clip < 0 or a non-finite clip; horizontal_fov_deg outside (0, 180); noise < 0. */
+typedef struct hg_depth_cam {
+  int32_t width, height;          /* W, H in pixels */
+  float horizontal_fov_deg;       /* pinhole, square pixels: fx = (W/2) / tan(fov/2) */
+  float pos[3];                   /* camera position in the base frame */
+  float near_clip, far_clip;      /* metres, planar depth */
+  int32_t normalize;              /* 0: metres; 1: (d - near)/(far - near) - 0.5 */
+  float noise;                    /* uniform +-noise metres added before the clip; 0 = none */
+} hg_depth_cam;
+int hg_render_depth(void* sim, const hg_depth_cam* cam, const float* pitch, float* out, int64_t env_stride,
+                    uint64_t counter, void* stream);
+
 /* ---- rollout storage: fused GAE (replaces RolloutStorage.compute_returns,
  * humanoid/algo/ppo/rollout_storage.py:122-143) ---- */
 /* Pass 1: reverse-time scan.  rewards/values/returns/advantages [T,N] f32, dones [T,N] u8,
