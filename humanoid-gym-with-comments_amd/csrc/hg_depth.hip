@@ -96,6 +96,12 @@ __host__ __device__ inline float depth_march(bool field, const int16_t* __restri
         if (t0 <= t1) {
           int ci = (int)floorf(fmaf(t0, dgx, u0)), cj = (int)floorf(fmaf(t0, dgy, v0));
           const int sx = dgx > 0.f ? 1 : -1, sy = dgy > 0.f ? 1 : -1;
+          // the surface's boundary is closed: a ray that starts on u == rows - 1 (v == cols - 1) and does
+          // not move inward is in the last cell at u = 1 (v = 1), as in ground(); one moving inward gets
+          // there by the zero-length first segment
+          const bool ei = dgx >= 0.f && i0 + ci == rows - 1, ej = dgy >= 0.f && j0 + cj == C - 1;
+          ci -= ei;
+          cj -= ej;
           float ts = t0;
           int prev = 0;  // sign g ended the previous segment with (0: none)
           const float ddiag = dgx - dgy, idiag = 1.0f / ddiag;  // idiag unused when ddiag == 0
