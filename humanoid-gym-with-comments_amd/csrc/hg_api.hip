@@ -19,6 +19,11 @@ extern "C" int hg_launch_actuator_draw(const HgState* S, uint64_t counter, int m
                                        hipStream_t stream);
 extern "C" int hg_launch_depth(const HgState* S, const hg_cfg* hcfg, const hg_depth_cam* cam, const float* pitch,
                                float* out, int64_t env_stride, uint64_t counter, int mapping, hipStream_t stream);
+extern "C" int hg_launch_view_pose(const HgState* S, const hg_model* model, const int32_t* env_ids, int n, float* out,
+                                   int* num_shapes, hipStream_t stream);
+extern "C" int hg_launch_view(const HgState* S, const hg_cfg* hcfg, const hg_view_cam* cam, const double* fwd,
+                              const double* left, const double* up, const int32_t* env_ids, int n, int num_shapes,
+                              const float* table, uint8_t* rgb, float* depth, uint8_t* ids, hipStream_t stream);
 
 namespace {
 
@@ -39,7 +44,7 @@ struct Layout {
   size_t off[HG_T_COUNT + 8];
   size_t bytes;
   // extra regions
-  size_t obs_buf, priv_buf, frame_obs, frame_priv, cfg, model, obs_noise, noise_counter, env_rows, env_order;
+  size_t obs_buf, priv_buf, frame_obs, frame_priv, cfg, model, obs_noise, noise_counter, env_rows, env_order, view_table;
 };
 
 enum { X_OBS0 = HG_T_COUNT, X_OBS1, X_PRIV0, X_PRIV1, X_FOBS, X_FPRIV, X_CFG, X_MODEL };
@@ -117,6 +122,7 @@ Layout make_layout(const hg_cfg* c) {
   L.noise_counter = o; o += align256(sizeof(uint64_t));
   L.env_rows = o; o += align256((size_t)np * 4);
   L.env_order = o; o += align256((size_t)np * 4);
+  L.view_table = o; o += align256((size_t)n * 16 * 16 * 4);  // hg_render_view's world shape table, a row per selected env
   L.off[HG_T_OBS_BUF] = L.obs_buf;
   L.off[HG_T_PRIV_BUF] = L.priv_buf;
   L.off[HG_T_ENV_ROWS] = L.env_rows;
@@ -585,6 +591,59 @@ extern "C" int hg_render_depth(void* sim, const hg_depth_cam* cam, const float* 
   const int mapping = (m && strcmp(m, "rows") == 0) ? 1 : 0;
   if (hg_launch_depth(&s->S, &s->cfg, cam, pitch, out, env_stride, counter, mapping, (hipStream_t)stream) != 0)
     return fail(s, HG_ERR_HIP, "k_depth launch failed");
+  return HG_OK;
+}
+
+// ---- follow-camera view (hg_view.hip): argument checks here, nothing is launched on a refusal
+extern "C" int hg_view_shapes(void* sim, const int32_t* env_ids, int n, float* out, int32_t* num_shapes, void* stream) {
+  Sim* s = (Sim*)sim;
+  if (!s) return fail(s, HG_ERR_ARG, "hg_view_shapes: sim is NULL");
+  if (!out) return fail(s, HG_ERR_ARG, "hg_view_shapes: out is NULL");
+  if (n <= 0 || n > s->S.n) return fail(s, HG_ERR_ARG, "hg_view_shapes: n must be in [1, num_envs]");
+  int ns = 0;
+  if (hg_launch_view_pose(&s->S, &s->model, env_ids, n, out, &ns, (hipStream_t)stream) != 0)
+    return fail(s, HG_ERR_HIP, "k_view_pose launch failed");
+  if (num_shapes) *num_shapes = ns;
+  return HG_OK;
+}
+
+extern "C" int hg_render_view(void* sim, const hg_view_cam* cam, const int32_t* env_ids, int n, uint8_t* rgb,
+                              float* depth, uint8_t* ids, void* stream) {
+  Sim* s = (Sim*)sim;
+  if (!s) return fail(s, HG_ERR_ARG, "hg_render_view: sim is NULL");
+  if (!cam) return fail(s, HG_ERR_ARG, "hg_render_view: cam is NULL");
+  if (!rgb && !depth && !ids) return fail(s, HG_ERR_ARG, "hg_render_view: rgb, depth and ids are all NULL");
+  if (cam->width <= 0 || cam->height <= 0) return fail(s, HG_ERR_ARG, "hg_render_view: width and height must be > 0");
+  const int64_t wh = (int64_t)cam->width * cam->height;
+  if (wh > (int64_t)1920 * 1080) return fail(s, HG_ERR_ARG, "hg_render_view: width * height above 1920 * 1080");
+  if (n <= 0 || n > s->S.n) return fail(s, HG_ERR_ARG, "hg_render_view: n must be in [1, num_envs]");
+  if ((int64_t)n * wh >= ((int64_t)1 << 31)) return fail(s, HG_ERR_ARG, "hg_render_view: n * width * height must stay below 2^31");
+  if (!(cam->horizontal_fov_deg > 0.f) || !(cam->horizontal_fov_deg < 180.f))
+    return fail(s, HG_ERR_ARG, "hg_render_view: horizontal_fov_deg must be inside (0, 180)");
+  if (!(cam->far_clip > 0.f) || !(cam->far_clip < INFINITY))
+    return fail(s, HG_ERR_ARG, "hg_render_view: far_clip must be finite and > 0");
+  if (cam->mode != 0 && cam->mode != 1) return fail(s, HG_ERR_ARG, "hg_render_view: mode must be 0 (world) or 1 (follow)");
+  double f[3], nrm = 0.0;
+  for (int i = 0; i < 3; i++) {
+    if (!std::isfinite(cam->eye[i]) || !std::isfinite(cam->target[i]))
+      return fail(s, HG_ERR_ARG, "hg_render_view: eye and target must be finite");
+    f[i] = (double)cam->target[i] - (double)cam->eye[i];
+    nrm += f[i] * f[i];
+  }
+  if (!(nrm > 0.0)) return fail(s, HG_ERR_ARG, "hg_render_view: eye equals target");
+  nrm = sqrt(nrm);
+  for (int i = 0; i < 3; i++) f[i] /= nrm;
+  // left = normalize(z x f), up = f x left
+  const double lx = -f[1], ly = f[0], ln = sqrt(lx * lx + ly * ly);
+  if (!(ln > 1e-6)) return fail(s, HG_ERR_ARG, "hg_render_view: the view direction (target - eye) is parallel to +z: no up vector");
+  const double left[3] = {lx / ln, ly / ln, 0.0};
+  const double up[3] = {f[1] * left[2] - f[2] * left[1], f[2] * left[0] - f[0] * left[2], f[0] * left[1] - f[1] * left[0]};
+  float* table = (float*)(s->arena + s->L.view_table);
+  int ns = 0;
+  if (hg_launch_view_pose(&s->S, &s->model, env_ids, n, table, &ns, (hipStream_t)stream) != 0)
+    return fail(s, HG_ERR_HIP, "k_view_pose launch failed");
+  if (hg_launch_view(&s->S, &s->cfg, cam, f, left, up, env_ids, n, ns, table, rgb, depth, ids, (hipStream_t)stream) != 0)
+    return fail(s, HG_ERR_HIP, "k_view launch failed");
   return HG_OK;
 }
 

@@ -158,6 +158,7 @@ __host__ __device__ inline float depth_march(bool field, const int16_t* __restri
   return t;
 }
 
+#ifndef HG_DEPTH_MARCH_ONLY  // hg_view.hip includes this file for depth_march alone
 // TILE: a wave is an 8 x 8 pixel tile (its 64 rays walk the same few cells); else 64 consecutive
 // pixels of the row-major image.
 template <bool TILE>
@@ -214,8 +215,11 @@ __global__ __launch_bounds__(DEPTH_T, 8) void k_depth(HgState S, DepthParams P, 
   }
 }
 
+#endif
+
 }  // namespace
 
+#ifndef HG_DEPTH_MARCH_ONLY
 // mapping: 0 = 8 x 8 pixel tile per wave, 1 = 64 consecutive row-major pixels per wave.  The
 // arguments were checked by hg_render_depth.
 extern "C" int hg_launch_depth(const HgState* S, const hg_cfg* hcfg, const hg_depth_cam* cam, const float* pitch,
@@ -258,3 +262,4 @@ extern "C" int hg_launch_depth(const HgState* S, const hg_cfg* hcfg, const hg_de
   }
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
+#endif

@@ -128,6 +128,54 @@ def depth_cam(depth_cfg, normalize=None, noise=None, env_stride=None):
     return cam
 
 
+class HgViewCam(ctypes.Structure):
+    """hg_view_cam (include/hgsim.h): the world or follow camera hg_render_view renders."""
+    _fields_ = [("width", i32), ("height", i32), ("horizontal_fov_deg", f32), ("mode", i32), ("eye", f32 * 3),
+                ("target", f32 * 3), ("far_clip", f32)]
+
+
+VIEW_MAX_PIXELS = 1920 * 1080  # hg_render_view: W * H bound
+VIEW_MAX_SHAPES = 16           # rows of a view_shapes table (hg_view_shapes.h HV_MAX_SHAPES), 16 floats each
+
+
+def view_cam(size, horizontal_fov, eye, target, far_clip, mode=1, n=1):
+    """HgViewCam for hg_render_view: size (W, H), mode 1 = follow (eye / target are offsets from the
+    base position, world axes), 0 = world camera.  Raises ValueError on everything hg_render_view
+    would refuse for n rendered envs (include/hgsim.h), so a bad camera fails before any launch."""
+    import math
+    w, h = (int(v) for v in size)
+    eye, target = [float(v) for v in eye], [float(v) for v in target]
+    if len(eye) != 3 or len(target) != 3:
+        raise ValueError("view camera: eye and target must have 3 entries")
+    cam = HgViewCam()
+    cam.width, cam.height = w, h
+    cam.horizontal_fov_deg = float(horizontal_fov)
+    cam.mode = int(mode)
+    for k in range(3):
+        cam.eye[k], cam.target[k] = eye[k], target[k]
+    cam.far_clip = float(far_clip)
+    if w <= 0 or h <= 0:
+        raise ValueError(f"view camera: size must be positive (W, H), got {(w, h)}")
+    if w * h > VIEW_MAX_PIXELS:
+        raise ValueError(f"view camera: {w} x {h} pixels exceed {VIEW_MAX_PIXELS}")
+    if n <= 0 or n * w * h >= 2 ** 31:
+        raise ValueError(f"view camera: need n > 0 and n * W * H < 2^31, got n = {n}")
+    if not (0.0 < cam.horizontal_fov_deg < 180.0):
+        raise ValueError(f"view camera: horizontal_fov must be inside (0, 180), got {cam.horizontal_fov_deg}")
+    if not (0.0 < cam.far_clip < float("inf")):
+        raise ValueError(f"view camera: far_clip must be finite and > 0, got {cam.far_clip}")
+    if cam.mode not in (0, 1):
+        raise ValueError(f"view camera: mode must be 0 (world) or 1 (follow), got {cam.mode}")
+    if not all(math.isfinite(v) for v in list(cam.eye) + list(cam.target)):
+        raise ValueError("view camera: eye and target must be finite")
+    d = [cam.target[k] - cam.eye[k] for k in range(3)]
+    if d == [0.0, 0.0, 0.0]:
+        raise ValueError("view camera: eye equals target")
+    if math.hypot(d[0], d[1]) <= 1e-6 * math.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]):
+        raise ValueError("view camera: the view direction (target - eye) is parallel to +z: no up vector")
+    return cam
+
+
 # tensor ids (enum hg_tensor_id)
 TENSOR_IDS = [
     "ROOT_STATE", "DOF_POS", "DOF_VEL", "CONTACT_FORCES", "RIGID_STATE", "TORQUES", "ACTIONS",
@@ -147,7 +195,7 @@ EXPORTS = ["hg_arena_bytes", "hg_create", "hg_destroy", "hg_last_error", "hg_ten
            "hg_post", "hg_set_rollout_sink", "hg_ep_stats_slot", "hg_obs_head", "hg_obs_window_advance", "hg_update_cfg", "hg_reset_masked",
            "hg_set_command_range_x", "hg_publish_terrain_level", "hg_set_dof_state_indexed", "hg_set_root_state_indexed",
            "hg_set_root_state", "hg_set_env_props", "hg_set_actuator_props",
-           "hg_measure_heights", "hg_render_depth", "hg_gae_scan", "hg_gae_stats_len", "hg_gae_normalize", "hg_adam_step", "hg_adam_chunk", "hg_kl_mean", "hg_kl_lr_rule",
+           "hg_measure_heights", "hg_render_depth", "hg_view_shapes", "hg_render_view", "hg_gae_scan", "hg_gae_stats_len", "hg_gae_normalize", "hg_adam_step", "hg_adam_chunk", "hg_kl_mean", "hg_kl_lr_rule",
            "hg_rollout_act", "hg_rollout_act_head", "hg_rollout_act_tail", "hg_rollout_env", "hg_gather_rows", "hg_gather_rows_ex", "hg_gather_stacked", "hg_ppo_loss", "hg_ppo_loss_lr", "hg_ppo_loss_scratch", "hg_ppo_loss_backward",
            "hg_mirror_rows", "hg_sym_loss", "hg_sym_loss_scratch", "hg_sym_loss_backward",
            "hg_mlp_act_backward", "hg_mlp_act_backward_scratch", "hg_colsum_jobs", "hg_linear_skinny_supported",
@@ -171,14 +219,14 @@ class GatherTable(ctypes.Structure):
 
 def source_hash(pkg_root=PKG_ROOT):
     """sha256 (first 16 hex digits) of the library's sources in the Makefile's stamp order (SRCS,
-    csrc/hg_common.h, include/hgsim.h), as the Makefile computes it; None when the sources are
+    csrc/hg_common.h, csrc/hg_view_shapes.h, include/hgsim.h), as the Makefile computes it; None when the sources are
     not in the tree."""
     import hashlib
     try:
         with open(os.path.join(pkg_root, "Makefile")) as f:
             srcs = next(ln.split("=", 1)[1].split() for ln in f if ln.startswith("SRCS ="))
         h = hashlib.sha256()
-        for rel in srcs + ["csrc/hg_common.h", "../include/hgsim.h"]:
+        for rel in srcs + ["csrc/hg_common.h", "csrc/hg_view_shapes.h", "../include/hgsim.h"]:
             with open(os.path.join(pkg_root, rel), "rb") as f:
                 h.update(f.read())
         return h.hexdigest()[:16]
@@ -237,6 +285,10 @@ def load_library(path=LIB_PATH):
     L.hg_measure_heights.argtypes = [vp, vp, ctypes.c_int, vp, vp]
     L.hg_render_depth.restype = ctypes.c_int
     L.hg_render_depth.argtypes = [vp, ctypes.POINTER(HgDepthCam), vp, vp, ctypes.c_int64, ctypes.c_uint64, vp]
+    L.hg_view_shapes.restype = ctypes.c_int
+    L.hg_view_shapes.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_int32), vp]
+    L.hg_render_view.restype = ctypes.c_int
+    L.hg_render_view.argtypes = [vp, ctypes.POINTER(HgViewCam), vp, ctypes.c_int, vp, vp, vp, vp]
     L.hg_set_root_state.restype = ctypes.c_int
     L.hg_set_root_state.argtypes = [vp, vp, vp]
     L.hg_set_env_props.restype = ctypes.c_int

@@ -129,6 +129,14 @@ class XBotLCfg(BaseConfig):
         ref_env = 0
         pos = [10, 0, 6]
         lookat = [11.0, 5, 3.0]
+        # the follow camera of env.render_view / play.py --record (BUILD-DEFINED; the reference's
+        # play.py:84-103 hard-codes a 1920 x 1080 sensor and FOLLOW_POSITION): offsets from the base
+        # position in world axes
+        record_size = (640, 360)
+        horizontal_fov = 60
+        follow_offset = [2.0, -2.0, 0.8]
+        follow_target = [0, 0, -0.2]
+        far_clip = 50.0
 
     class init_state:
         pos = [0.0, 0.0, 0.95]

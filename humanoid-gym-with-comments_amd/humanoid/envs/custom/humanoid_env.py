@@ -378,6 +378,69 @@ class XBotLFreeEnv(BaseTask):
         self._launch_depth(cam, out, h * w, self.common_step_counter)
         return out
 
+    # ------------------------------------------------------------------ follow-camera view
+    def _view_env_ids(self, env_ids):
+        """(device int32 tensor or None, n) for hg_view_shapes / hg_render_view."""
+        if env_ids is None:
+            return None, self.num_envs
+        ids = torch.as_tensor(env_ids, device=self.device).to(torch.int32).contiguous().view(-1)
+        if ids.numel() == 0 or ids.numel() > self.num_envs:
+            raise ValueError(f"env_ids must name between 1 and {self.num_envs} envs, got {ids.numel()}")
+        return ids, int(ids.numel())
+
+    def default_view_cam(self, follow=True, n=1):
+        """The camera of cfg.viewer: the follow camera (record_size, horizontal_fov, follow_offset,
+        follow_target, far_clip; BUILD-DEFINED) or, follow=False, the world camera viewer.pos ->
+        viewer.lookat."""
+        v = self.cfg.viewer
+        if follow:
+            return N.view_cam(v.record_size, v.horizontal_fov, v.follow_offset, v.follow_target, v.far_clip, mode=1, n=n)
+        return N.view_cam(v.record_size, v.horizontal_fov, v.pos, v.lookat, v.far_clip, mode=0, n=n)
+
+    def view_shapes(self, env_ids=None):
+        """World shape table [n, num_shapes, 16] of the drawn shapes (hg_view_shapes, include/hgsim.h):
+        forward kinematics of the current root_states and dof_pos."""
+        ids, n = self._view_env_ids(env_ids)
+        out = torch.empty(n, N.VIEW_MAX_SHAPES, 16, dtype=torch.float32, device=self.device)
+        ns = ctypes.c_int32(0)
+        N.check(self.hg.hg_view_shapes(self.sim, None if ids is None else ctypes.c_void_p(ids.data_ptr()), n,
+                                       ctypes.c_void_p(out.data_ptr()), ctypes.byref(ns), self._stream()), self.sim)
+        return out[:, :ns.value]
+
+    def render_view(self, env_ids=None, cam=None, rgb=None, depth=None, ids=None, want=("rgb",)):
+        """Render robot and terrain (hg_render_view, include/hgsim.h) for env_ids (None: all envs)
+        with `cam` (an _native.view_cam; None: the follow camera of cfg.viewer).  Returns the
+        requested tensors in the order of `want`, a subset of ("rgb", "depth", "ids"): rgb uint8
+        [n, H, W, 3], depth float32 [n, H, W] metres, ids uint8 [n, H, W]; a tensor passed as rgb /
+        depth / ids is written in place and is part of the request."""
+        eids, n = self._view_env_ids(env_ids)
+        if cam is None:
+            cam = self.default_view_cam(True, n)
+        h, w = cam.height, cam.width
+        N.view_cam((w, h), cam.horizontal_fov_deg, cam.eye, cam.target, cam.far_clip, cam.mode, n)  # validates
+        spec = {"rgb": (rgb, torch.uint8, (n, h, w, 3)), "depth": (depth, torch.float32, (n, h, w)),
+                "ids": (ids, torch.uint8, (n, h, w))}
+        want = tuple(want)
+        bad = [k for k in want if k not in spec]
+        if bad:
+            raise ValueError(f"render_view: want holds {bad}; choose from ('rgb', 'depth', 'ids')")
+        bufs = {}
+        for name, (given, dt, shape) in spec.items():
+            if given is not None:
+                if (given.dtype != dt or tuple(given.shape) != shape or not given.is_contiguous()
+                        or given.device != self.device):
+                    raise ValueError(f"render_view: {name} must be a contiguous {dt} {list(shape)} tensor on {self.device}")
+                bufs[name] = given
+            elif name in want:
+                bufs[name] = torch.empty(shape, dtype=dt, device=self.device)
+        if not bufs:
+            raise ValueError("render_view: nothing requested")
+        p = lambda k: ctypes.c_void_p(bufs[k].data_ptr()) if k in bufs else None  # noqa: E731
+        N.check(self.hg.hg_render_view(self.sim, ctypes.byref(cam), None if eids is None else ctypes.c_void_p(eids.data_ptr()),
+                                       n, p("rgb"), p("depth"), p("ids"), self._stream()), self.sim)
+        out = tuple(bufs[k] for k in want)
+        return out[0] if len(out) == 1 else out
+
     def _view(self, tid):
         d = N.HgDesc()
         N.check(self.hg.hg_tensor(self.sim, tid, ctypes.byref(d)), self.sim)

@@ -378,6 +378,50 @@ typedef struct hg_depth_cam {
 int hg_render_depth(void* sim, const hg_depth_cam* cam, const float* pitch, float* out, int64_t env_stride,
                     uint64_t counter, void* stream);
 
+/* ---- follow-camera view of robot and terrain (replaces the camera sensor play.py attaches and its
+ * IMAGE_COLOR read, scripts/play.py:84-141; BUILD-DEFINED: ray casting by a HIP kernel, no graphics
+ * pipeline) ----
+ * Standalone calls like hg_render_depth: they read root_states, dof_pos, the model and the terrain
+ * fields of the device hg_cfg, write only their outputs (and a private table region of the arena),
+ * allocate nothing and do not synchronise (capturable).  The pose is forward kinematics of
+ * root_states and dof_pos, NOT HG_T_RIGID_STATE: an env that was just reset, or whose state was
+ * written through the views, is drawn where it now is.
+ * Shapes (csrc/hg_view_shapes.h has the table's derivation, the ray rules and the shading
+ * constants): the model's kind-0 capsules, one box per foot (BUILD-DEFINED visual fit around the
+ * sole points) and the base box; arms above the wrist, neck and head are not collision shapes and
+ * are not drawn.  hg_view_shapes writes the world table: out[k][s][16] for selected env k and
+ * shape s < *num_shapes (host int, optional): [0] kind (0 capsule, 1 foot box, 2 base box; -1 in
+ * unused rows), capsule: [1..3] p0, [4..6] p1, [7] r; box: [1..3] centre, [4..6] half extents,
+ * [7..10] rotation xyzw.
+ * Camera: frame x forward / y left / z up with up = world +z; forward = normalize(target - eye);
+ * mode 0 takes eye and target as world points, mode 1 (follow) adds the env's base position to
+ * both (world axes: the camera translates with the robot and does not rotate with it, play.py:96-103).
+ * Pixels as hg_render_depth: row 0 top, column 0 left, direction (1, -(c + 0.5 - W/2) / fx,
+ * -(r + 0.5 - H/2) / fx) in the camera frame, and the ray parameter t is the planar depth.
+ * Scene: hg_render_depth's terrain (two-sided) plus the shapes; the nearest t in [0, far_clip]
+ * wins, a terrain/shape tie goes to the shape, shape ties to the lower index, an eye inside a
+ * shape gives t = 0 with that shape, a non-finite pose draws no shape (and, in follow mode,
+ * nothing at all).
+ * Outputs (each optional, not all NULL), for selected env k: rgb u8 [n, H, W, 3]; depth f32
+ * [n, H, W] = t in metres, far_clip when nothing is hit; ids u8 [n, H, W]: 0 sky, 1 terrain,
+ * 2 + s shape s.  env_ids: device i32 [n], NULL = envs 0 .. n-1 (an id outside [0, num_envs) draws
+ * an empty row).
+ * HG_ERR_ARG before any launch (hg_last_error names the argument): sim or cam (out for
+ * hg_view_shapes) NULL; all three outputs NULL; W or H <= 0; W * H > 1920 * 1080; n <= 0,
+ * n > num_envs or n * W * H >= 2^31; horizontal_fov_deg outside (0, 180); far_clip non-finite or
+ * <= 0; a mode other than 0 / 1; a non-finite eye or target; eye equal to target; a view direction
+ * parallel to +z (no up vector). */
+typedef struct hg_view_cam {
+  int32_t width, height;
+  float horizontal_fov_deg;
+  int32_t mode;             /* 0: world camera (eye, target); 1: follow: base position + eye[] / target[] */
+  float eye[3], target[3];  /* up is world +z */
+  float far_clip;
+} hg_view_cam;
+int hg_view_shapes(void* sim, const int32_t* env_ids, int n, float* out, int32_t* num_shapes, void* stream);
+int hg_render_view(void* sim, const hg_view_cam* cam, const int32_t* env_ids, int n, uint8_t* rgb, float* depth,
+                   uint8_t* ids, void* stream);
+
 /* ---- rollout storage: fused GAE (replaces RolloutStorage.compute_returns,
  * humanoid/algo/ppo/rollout_storage.py:122-143) ---- */
 /* Pass 1: reverse-time scan.  rewards/values/returns/advantages [T,N] f32, dones [T,N] u8,
