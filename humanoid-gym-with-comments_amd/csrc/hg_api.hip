@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "hg_common.h"
+#include "hg_metrics_sample.h"  // HG_METRICS_SLOTS / HG_METRICS_COUNTS
 
 extern "C" int hg_launch_step(const HgState* S, const hg_cfg* hcfg, const float* actions, uint64_t step_counter,
                                int per_env_actuators, hipStream_t stream);
@@ -24,6 +25,9 @@ extern "C" int hg_launch_view_pose(const HgState* S, const hg_model* model, cons
 extern "C" int hg_launch_view(const HgState* S, const hg_cfg* hcfg, const hg_view_cam* cam, const double* fwd,
                               const double* left, const double* up, const int32_t* env_ids, int n, int num_shapes,
                               const float* table, uint8_t* rgb, float* depth, uint8_t* ids, hipStream_t stream);
+extern "C" int hg_launch_metrics_sample(const HgState* S, const HgMetrics* M, double dt, hipStream_t stream);
+extern "C" int hg_launch_metrics_fold(const HgState* S, const HgMetrics* M, int mode, const uint8_t* mask,
+                                      hipStream_t stream);
 
 namespace {
 
@@ -31,13 +35,13 @@ thread_local std::string g_create_error;
 
 struct Field {
   int id;
-  int dtype;      // 0 f32, 1 i64, 2 u8, 3 i32
+  int dtype;      // 0 f32, 1 i64, 2 u8, 3 i32, 4 f64
   int rows;       // SoA rows per env (ignored for special)
   int ndim;       // view ndim
   int64_t shp[3]; // trailing dims of the [N, ...] view (row index = r0*shp... see make_desc)
 };
 
-size_t esize(int dtype) { return dtype == 1 ? 8 : (dtype == 2 ? 1 : 4); }
+size_t esize(int dtype) { return (dtype == 1 || dtype == 4) ? 8 : (dtype == 2 ? 1 : 4); }
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Layout {
@@ -75,7 +79,8 @@ int dtype_of(int id) {
     case HG_T_RESET_BUF: case HG_T_TIME_OUT_BUF: case HG_T_LAST_CONTACTS: return 2;
     case HG_T_EPISODE_LENGTH: return 1;
     case HG_T_NONFINITE: case HG_T_TERRAIN_LEVEL: case HG_T_TERRAIN_TYPE: case HG_T_ROWS_DROPPED:
-    case HG_T_ENV_ROWS: case HG_T_ENV_ORDER: return 3;
+    case HG_T_ENV_ROWS: case HG_T_ENV_ORDER: case HG_T_METRICS_COUNT: return 3;
+    case HG_T_METRICS_RUN: case HG_T_METRICS_DONE: return 4;
     default: return 0;
   }
 }
@@ -107,6 +112,12 @@ Layout make_layout(const hg_cfg* c) {
     // CMD_RANGE_X region: the live range [2], then the latest mean terrain level [1]
     if (id == HG_T_CMD_RANGE_X) { o += align256(3 * sizeof(float)); continue; }
     if (id == HG_T_CURRICULUM_RING) { o += align256((size_t)HG_EP_RING * 2 * sizeof(float)); continue; }
+    // the gait-metrics accumulators exist only with cfg.gait_metrics: off, the layout is what it was
+    if (id == HG_T_METRICS_RUN || id == HG_T_METRICS_DONE || id == HG_T_METRICS_COUNT) {
+      if (c->gait_metrics)
+        o += align256((size_t)(id == HG_T_METRICS_COUNT ? HG_METRICS_COUNTS : HG_METRICS_SLOTS) * np * esize(dtype_of(id)));
+      continue;
+    }
     o += align256((size_t)soa_rows(id) * np * esize(dtype_of(id)));
   }
   // the observation histories: one sliding window per env row (hg_obs_window_frames)
@@ -138,6 +149,7 @@ struct Sim {
   size_t bytes;
   Layout L;
   HgState S;
+  HgMetrics M{nullptr, nullptr, nullptr};  // hg_cfg.gait_metrics: the accumulators (NULL: off)
   int head;    // first window slot of the current observation stack
   uint64_t post_seq = 0;  // post/reset launches so far: EP_STATS ring row of the next one
   int ep_slot = 0;        // ring row written by the latest one
@@ -304,6 +316,8 @@ int hg_create(const hg_cfg* cfg, const hg_model* model, void* arena, size_t aren
   S.kp_scale = (float*)P(HG_T_KP_SCALE);
   S.kd_scale = (float*)P(HG_T_KD_SCALE);
   S.armature_add = (float*)P(HG_T_ARMATURE_ADD);
+  if (cfg->gait_metrics)  // zeroed with the arena below
+    s->M = HgMetrics{(double*)P(HG_T_METRICS_RUN), (double*)P(HG_T_METRICS_DONE), (int32_t*)P(HG_T_METRICS_COUNT)};
   {
     // K_step's wave balancing (hg_common.h hg_env_order_block, run by the post launch): on unless HG_WAVE_BALANCE=0
     const char* wb = getenv("HG_WAVE_BALANCE");
@@ -370,6 +384,11 @@ int hg_tensor(void* sim, int id, hg_desc* d) {
     case HG_T_RIGID_STATE:     // [N,13,13] (rigid_body_state.view(N,-1,13)'s shape), SoA storage
       d->ndim = 3; d->shape[0] = n; d->shape[1] = HG_NB; d->shape[2] = 13;
       d->strides[0] = 1; d->strides[1] = 13 * np; d->strides[2] = np;
+      return HG_OK;
+    case HG_T_METRICS_RUN: case HG_T_METRICS_DONE: case HG_T_METRICS_COUNT:
+      if (!s->cfg.gait_metrics) return fail(s, HG_ERR_ARG, "hg_tensor: gait metrics are off for this sim (hg_cfg.gait_metrics)");
+      d->ndim = 2; d->shape[0] = id == HG_T_METRICS_COUNT ? HG_METRICS_COUNTS : HG_METRICS_SLOTS; d->shape[1] = n;
+      d->strides[0] = np; d->strides[1] = 1;
       return HG_OK;
     case HG_T_EPISODE_SUMS:
       d->ndim = 2; d->shape[0] = HG_NUM_REWARDS; d->shape[1] = n; d->strides[0] = np; d->strides[1] = 1;
@@ -467,7 +486,8 @@ int hg_update_cfg(void* sim, const hg_cfg* cfg, void* stream) {
       cfg->decimation != o.decimation || cfg->terrain_type != o.terrain_type || cfg->hf_rows != o.hf_rows ||
       cfg->hf_cols != o.hf_cols || cfg->heightfield != o.heightfield || cfg->terrain_origins != o.terrain_origins ||
       cfg->terrain_rows != o.terrain_rows || cfg->terrain_cols != o.terrain_cols ||
-      cfg->critic_heights != o.critic_heights || cfg->critic_height_points != o.critic_height_points)
+      cfg->critic_heights != o.critic_heights || cfg->critic_height_points != o.critic_height_points ||
+      (cfg->gait_metrics != 0) != (o.gait_metrics != 0))
     return fail(s, HG_ERR_ARG, "hg_update_cfg: layout fields cannot change after hg_create");
   if (cfg->pgs_iterations < 0 || cfg->pgs_iterations > 1000 || !(cfg->sim_dt > 0.f))
     return fail(s, HG_ERR_ARG, "hg_update_cfg: bad solver parameters");
@@ -568,6 +588,46 @@ extern "C" int hg_measure_heights(void* sim, const float* points_xy, int num_poi
   hipLaunchKernelGGL(k_heights, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s->S,
                      points_xy, num_points, out);
   return hipGetLastError() == hipSuccess ? HG_OK : fail(s, HG_ERR_HIP, "k_heights launch failed");
+}
+
+// ---- gait metrics (hg_metrics.hip): argument checks here, nothing is launched on a refusal
+static Sim* metrics_sim(void* sim, const char* who) {
+  Sim* s = (Sim*)sim;
+  if (!s) { fail(nullptr, HG_ERR_ARG, std::string(who) + ": sim is NULL"); return nullptr; }
+  if (!s->cfg.gait_metrics) {
+    fail(s, HG_ERR_ARG, std::string(who) + ": gait metrics are off for this sim (hg_cfg.gait_metrics)");
+    return nullptr;
+  }
+  return s;
+}
+
+extern "C" int hg_metrics_sample(void* sim, void* stream) {
+  Sim* s = metrics_sim(sim, "hg_metrics_sample");
+  if (!s) return HG_ERR_ARG;
+  const double dt = (double)s->cfg.sim_dt * (double)s->cfg.decimation;  // the policy step
+  if (hg_launch_metrics_sample(&s->S, &s->M, dt, (hipStream_t)stream) != 0)
+    return fail(s, HG_ERR_HIP, "k_metrics_sample launch failed");
+  return HG_OK;
+}
+
+extern "C" int hg_metrics_fold(void* sim, int mode, const uint8_t* mask, void* stream) {
+  Sim* s = metrics_sim(sim, "hg_metrics_fold");
+  if (!s) return HG_ERR_ARG;
+  if (mode != 0 && mode != 1) return fail(s, HG_ERR_ARG, "hg_metrics_fold: mode must be 0 (episode end) or 1 (discard)");
+  if (hg_launch_metrics_fold(&s->S, &s->M, mode, mode == 1 ? mask : nullptr, (hipStream_t)stream) != 0)
+    return fail(s, HG_ERR_HIP, "k_metrics_fold launch failed");
+  return HG_OK;
+}
+
+extern "C" int hg_metrics_clear(void* sim, void* stream) {
+  Sim* s = metrics_sim(sim, "hg_metrics_clear");
+  if (!s) return HG_ERR_ARG;
+  // the three regions are neighbours in the arena (make_layout): one memset from the first to the arena's next region
+  const size_t lo = s->L.off[HG_T_METRICS_RUN];
+  const size_t hi = s->L.off[HG_T_METRICS_COUNT] + align256((size_t)HG_METRICS_COUNTS * s->S.np * sizeof(int32_t));
+  if (hipMemsetAsync(s->arena + lo, 0, hi - lo, (hipStream_t)stream) != hipSuccess)
+    return fail(s, HG_ERR_HIP, "hg_metrics_clear: memset failed");
+  return HG_OK;
 }
 
 // ---- depth camera (hg_depth.hip): argument checks here, nothing is launched on a refusal

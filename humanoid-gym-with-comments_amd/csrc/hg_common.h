@@ -74,6 +74,14 @@ struct HgState {
   float* armature_add;
 };
 
+// the gait-metrics accumulators (hg_cfg.gait_metrics, hg_metrics.hip), SoA with the arena's stride np;
+// held by the sim next to HgState, not inside it: the other kernels' by-value argument stays as it is
+struct HgMetrics {
+  double* run;     // [13][np] HG_T_METRICS_RUN: the running episode's sums
+  double* done;    // [13][np] HG_T_METRICS_DONE: sums over the completed episodes
+  int32_t* count;  // [4][np]  HG_T_METRICS_COUNT: episodes, falls, time_outs, skipped
+};
+
 // what the statistics block of the post launch needs for the command curriculum and the curriculum
 // extras (hg_envlogic.hip); ring == NULL: neither is on, the block does what it did without them
 struct HgCurriculum {

@@ -76,7 +76,8 @@ class HgCfg(ctypes.Structure):
         ("max_episode_length_s", f32), ("env_offset", i32),
         ("actuator_rand", i32), ("act_kp_range", f32 * 2), ("act_kd_range", f32 * 2), ("act_strength_range", f32 * 2),
         ("act_armature_range", f32 * 2),
-        ("critic_heights", i32), ("critic_height_scale", f32), ("critic_height_points", ctypes.c_void_p),
+        ("critic_heights", i32), ("critic_height_scale", f32), ("gait_metrics", i32),
+        ("critic_height_points", ctypes.c_void_p),
         ("terrain_origins", ctypes.c_void_p),
         ("cmd_curriculum", i32), ("cmd_max_curriculum", f32),
     ]
@@ -184,18 +185,24 @@ TENSOR_IDS = [
     "FEET_AIR_TIME", "LAST_CONTACTS", "FEET_HEIGHT", "LAST_FEET_Z", "ENV_FRICTION", "BODY_MASS",
     "PUSH_FORCE", "PUSH_TORQUE", "BASE_LIN_VEL", "BASE_ANG_VEL", "PROJ_GRAVITY", "BASE_EULER",
     "REF_DOF_POS", "ENV_ORIGINS", "EP_STATS", "CONTACT_LAMBDA", "NONFINITE", "TERRAIN_LEVEL", "TERRAIN_TYPE",
-    "EP_STATS_RING", "ROWS_DROPPED", "ENV_ROWS", "ENV_ORDER",
+    "EP_STATS_RING", "ROWS_DROPPED", "METRICS_RUN", "METRICS_DONE", "METRICS_COUNT", "ENV_ROWS", "ENV_ORDER",
     "KP_SCALE", "KD_SCALE", "ARMATURE_ADD", "CMD_RANGE_X", "CURRICULUM_RING",
 ]
 EP_RING = 64  # HG_EP_RING
 T = {name: i for i, name in enumerate(TENSOR_IDS)}
+
+# gait metrics (hg_metrics_sample, include/hgsim.h): the slots of HG_T_METRICS_RUN / _DONE and the rows
+# of HG_T_METRICS_COUNT
+METRICS_NAMES = ["steps", "err_vx2", "err_vy2", "err_wz2", "distance", "work_pos", "torque2", "tilt2", "slip",
+                 "action_rate2", "double_support", "flight", "peak_torque"]
+METRICS_COUNT_NAMES = ["episodes", "falls", "time_outs", "skipped"]
 
 # every symbol include/hgsim.h declares (checked by tests/test_boundary.py)
 EXPORTS = ["hg_arena_bytes", "hg_create", "hg_destroy", "hg_last_error", "hg_tensor", "hg_step",
            "hg_post", "hg_set_rollout_sink", "hg_ep_stats_slot", "hg_obs_head", "hg_obs_window_advance", "hg_update_cfg", "hg_reset_masked",
            "hg_set_command_range_x", "hg_publish_terrain_level", "hg_set_dof_state_indexed", "hg_set_root_state_indexed",
            "hg_set_root_state", "hg_set_env_props", "hg_set_actuator_props",
-           "hg_measure_heights", "hg_render_depth", "hg_view_shapes", "hg_render_view", "hg_gae_scan", "hg_gae_stats_len", "hg_gae_normalize", "hg_adam_step", "hg_adam_chunk", "hg_kl_mean", "hg_kl_lr_rule",
+           "hg_measure_heights", "hg_metrics_sample", "hg_metrics_fold", "hg_metrics_clear", "hg_render_depth", "hg_view_shapes", "hg_render_view", "hg_gae_scan", "hg_gae_stats_len", "hg_gae_normalize", "hg_adam_step", "hg_adam_chunk", "hg_kl_mean", "hg_kl_lr_rule",
            "hg_rollout_act", "hg_rollout_act_head", "hg_rollout_act_tail", "hg_rollout_env", "hg_gather_rows", "hg_gather_rows_ex", "hg_gather_stacked", "hg_ppo_loss", "hg_ppo_loss_lr", "hg_ppo_loss_scratch", "hg_ppo_loss_backward",
            "hg_mirror_rows", "hg_sym_loss", "hg_sym_loss_scratch", "hg_sym_loss_backward",
            "hg_mlp_act_backward", "hg_mlp_act_backward_scratch", "hg_colsum_jobs", "hg_linear_skinny_supported",
@@ -219,14 +226,14 @@ class GatherTable(ctypes.Structure):
 
 def source_hash(pkg_root=PKG_ROOT):
     """sha256 (first 16 hex digits) of the library's sources in the Makefile's stamp order (SRCS,
-    csrc/hg_common.h, csrc/hg_view_shapes.h, include/hgsim.h), as the Makefile computes it; None when the sources are
+    csrc/hg_common.h, csrc/hg_view_shapes.h, csrc/hg_metrics_sample.h, include/hgsim.h), as the Makefile computes it; None when the sources are
     not in the tree."""
     import hashlib
     try:
         with open(os.path.join(pkg_root, "Makefile")) as f:
             srcs = next(ln.split("=", 1)[1].split() for ln in f if ln.startswith("SRCS ="))
         h = hashlib.sha256()
-        for rel in srcs + ["csrc/hg_common.h", "csrc/hg_view_shapes.h", "../include/hgsim.h"]:
+        for rel in srcs + ["csrc/hg_common.h", "csrc/hg_view_shapes.h", "csrc/hg_metrics_sample.h", "../include/hgsim.h"]:
             with open(os.path.join(pkg_root, rel), "rb") as f:
                 h.update(f.read())
         return h.hexdigest()[:16]
@@ -283,6 +290,12 @@ def load_library(path=LIB_PATH):
     L.hg_set_root_state_indexed.argtypes = [vp, vp, ctypes.c_int, vp, vp]
     L.hg_measure_heights.restype = ctypes.c_int
     L.hg_measure_heights.argtypes = [vp, vp, ctypes.c_int, vp, vp]
+    L.hg_metrics_sample.restype = ctypes.c_int
+    L.hg_metrics_sample.argtypes = [vp, vp]
+    L.hg_metrics_fold.restype = ctypes.c_int
+    L.hg_metrics_fold.argtypes = [vp, ctypes.c_int, vp, vp]
+    L.hg_metrics_clear.restype = ctypes.c_int
+    L.hg_metrics_clear.argtypes = [vp, vp]
     L.hg_render_depth.restype = ctypes.c_int
     L.hg_render_depth.argtypes = [vp, ctypes.POINTER(HgDepthCam), vp, vp, ctypes.c_int64, ctypes.c_uint64, vp]
     L.hg_view_shapes.restype = ctypes.c_int

@@ -7,6 +7,12 @@ Logging backends: TensorBoard's SummaryWriter when importable, otherwise a JSONL
 device tensors; the only host syncs per step are the ones the reference also has when log_dir is
 set (done-id extraction), so with log_dir=None the rollout is sync-free.
 With world_size > 1 (one process per GPU) every rank runs its env shard; rank 0 logs/saves.
+
+When the env accumulates gait metrics (metrics.gait, env.gait_report) every iteration's figures go
+into last_iteration_stats as gait_<name> and, with a log writer, into Gait/<name> scalars; the
+completed-episode accumulators are cleared behind the read, so each entry covers its own iteration.
+The read rides on the host waits the runner already has (the lazy path copies the accumulators to
+pinned memory behind the update and reads them one iteration later, like the loss means).
 """
 import json
 import os
@@ -190,9 +196,18 @@ class OnPolicyRunner:
                     copied.record()
                 else:  # the eager warm-up update returned host floats
                     host_means, copied = torch.tensor([float(x) for x in means3]), None
+                gait = None
+                if hasattr(self.env, "gait_pack"):
+                    # the accumulators follow the loss means to pinned memory; cleared behind the copy
+                    pack = self.env.gait_pack()
+                    gait_host = torch.empty(pack.shape, dtype=pack.dtype, pin_memory=True)
+                    gait_host.copy_(pack, non_blocking=True)
+                    self.env.clear_gait_metrics()
+                    gait = (gait_host, torch.cuda.Event())
+                    gait[1].record()
                 if pending is not None:
                     self._resolve_stats(*pending)
-                pending = (ev, host_means, copied)
+                pending = (ev, host_means, copied, gait)
                 ep_infos.clear()
                 continue
             mean_value_loss, mean_surrogate_loss, sym_loss, mean_base_lin_vel_loss = self.alg.update()
@@ -208,6 +223,12 @@ class OnPolicyRunner:
                                              lin_vel_loss=mean_base_lin_vel_loss)
             if self.alg.sym_loss:
                 self.last_iteration_stats["sym_loss"] = float(sym_loss)
+            gait = None
+            if hasattr(self.env, "gait_report"):
+                # after the update's own host wait: the iteration's completed episodes, then a fresh interval
+                gait = self.env.gait_report()
+                self.env.clear_gait_metrics()
+                self._add_gait_stats(gait)
             if self.log_dir is not None:
                 # the rollout's finished episodes in step order, env order within a step (the
                 # order the reference appends them in): one host read per iteration, after the
@@ -228,7 +249,10 @@ class OnPolicyRunner:
         if self.log_dir is not None:
             self.save(os.path.join(self.log_dir, "model_{}.pt".format(self.current_learning_iteration)))
 
-    def _resolve_stats(self, ev, host_means, copied):
+    def _add_gait_stats(self, report):
+        self.last_iteration_stats.update({"gait_" + k: v for k, v in report.items() if v is not None})
+
+    def _resolve_stats(self, ev, host_means, copied, gait=None):
         """last_iteration_stats from an iteration's phase events and its loss means (copied to
         pinned host memory behind that iteration's update; waits for that iteration's end only)."""
         ev[2].synchronize()
@@ -240,6 +264,9 @@ class OnPolicyRunner:
                                          value_loss=v, surrogate_loss=s, lin_vel_loss=lv)
         if sym:  # only with the symmetry loss on
             self.last_iteration_stats["sym_loss"] = sym[0]
+        if gait is not None:  # only with metrics.gait on
+            gait[1].synchronize()
+            self._add_gait_stats(self.env.gait_report_from_packed(gait[0].numpy()))
 
     def log(self, locs, width=90, pad=45):
         self.tot_timesteps += self.num_steps_per_env * self.env.num_envs
@@ -267,6 +294,11 @@ class OnPolicyRunner:
         w.add_scalar("Perf/total_fps", fps, it)
         w.add_scalar("Perf/collection time", locs["collection_time"], it)
         w.add_scalar("Perf/learning_time", locs["learn_time"], it)
+        gait_string = ""
+        for key, value in (locs.get("gait") or {}).items():  # only with metrics.gait on
+            if value is not None:
+                w.add_scalar("Gait/" + key, value, it)
+                gait_string += f"""{f'Gait {key}:':>{pad}} {value:.4f}\n"""
         if len(locs["rewbuffer"]) > 0:
             w.add_scalar("Train/mean_reward", statistics.mean(locs["rewbuffer"]), it)
             w.add_scalar("Train/mean_episode_length", statistics.mean(locs["lenbuffer"]), it)
@@ -282,7 +314,7 @@ class OnPolicyRunner:
         if len(locs["rewbuffer"]) > 0:
             s += (f"""{'Mean reward:':>{pad}} {statistics.mean(locs['rewbuffer']):.2f}\n"""
                   f"""{'Mean episode length:':>{pad}} {statistics.mean(locs['lenbuffer']):.2f}\n""")
-        s += ep_string
+        s += ep_string + gait_string
         s += (f"""{'-' * width}\n{'Total timesteps:':>{pad}} {self.tot_timesteps}\n"""
               f"""{'Iteration time:':>{pad}} {iteration_time:.2f}s\n{'Total time:':>{pad}} {self.tot_time:.2f}s\n"""
               f"""{'ETA:':>{pad}} {self.tot_time / (it + 1) * (locs['num_learning_iterations'] - it):.1f}s\n""")

@@ -112,6 +112,14 @@ class XBotLCfg(BaseConfig):
         dis_noise = 0.0                   # uniform +- metres added before the clip
         normalize = True                  # (d - near) / (far - near) - 0.5
 
+    class metrics:
+        # gait metrics per episode, accumulated on the device (BUILD-DEFINED: the reference only has
+        # Logger.log_rewards): command tracking, distance, cost of transport, foot slip, tilt, support
+        # phases, peak torque, falls against time-outs.  env.step() then brackets its post launch with
+        # hg_metrics_sample / hg_metrics_fold and env.gait_report() reads the figures; off, nothing
+        # of it exists and step() launches what it always did.
+        gait = False
+
     class noise:
         add_noise = True
         noise_level = 0.6

@@ -19,6 +19,11 @@ terrain heights under the sample grid, written on the device by the post launch'
 ``depth.use_camera`` (the reference's attach_camera, humanoid_env.py:399-423; values BUILD-DEFINED)
 adds a base-mounted depth camera rendered by hg_render_depth every ``depth.update_interval`` steps
 into the ring ``depth_buffer``; off (the default) nothing of it exists.
+
+``metrics.gait`` (BUILD-DEFINED) accumulates gait metrics per episode on the device: step() samples
+the pre-reset state between hg_step and hg_post (hg_metrics_sample) and folds finished episodes right
+after hg_post (hg_metrics_fold); ``gait_report()`` turns the accumulators into tracking errors, cost
+of transport, slip, support fractions and the fall rate.  Off (the default) nothing of it exists.
 """
 import ctypes
 
@@ -39,7 +44,59 @@ REWARD_NAMES = [
 ]
 assert REWARD_NAMES == sorted(REWARD_NAMES)
 
-_TORCH_DTYPES = {0: torch.float32, 1: torch.int64, 2: torch.uint8, 3: torch.int32}
+_TORCH_DTYPES = {0: torch.float32, 1: torch.int64, 2: torch.uint8, 3: torch.int32, 4: torch.float64}
+
+
+def _ratio(num, den):
+    return float(num) / float(den) if den > 0 else None
+
+
+def gait_report_row(done, counts, total_mass, gravity, dt):
+    """One row of gait figures from accumulator arrays, on the host in float64.
+    done: [13, n] completed-episode slot sums (HG_T_METRICS_DONE, slots _native.METRICS_NAMES);
+    counts: [4, n] episodes, falls, time_outs, skipped; total_mass: [n] kg, each env's whole robot;
+    gravity: m/s^2, positive; dt: the policy step.  A figure whose divisor is zero (no completed
+    episode, no distance) is None."""
+    # C-contiguous copies: numpy's sum order follows the memory layout, and the same envs must give
+    # the same figures whether they come as the whole array or as a terrain type's selection
+    d = np.ascontiguousarray(np.asarray(done, np.float64).reshape(len(N.METRICS_NAMES), -1))
+    c = np.ascontiguousarray(np.asarray(counts, np.int64).reshape(len(N.METRICS_COUNT_NAMES), -1))
+    m = np.asarray(total_mass, np.float64).reshape(-1)
+    tot = dict(zip(N.METRICS_NAMES, d.sum(axis=1)))
+    steps, dist = tot["steps"], tot["distance"]
+    episodes, falls, time_outs, skipped = (int(v) for v in c.sum(axis=1))
+
+    def rms(name):
+        v = _ratio(tot[name], steps)
+        return None if v is None else float(np.sqrt(v))
+    weight_dist = float((m * float(gravity) * d[N.METRICS_NAMES.index("distance")]).sum())
+    return {
+        "episodes": episodes, "falls": falls, "time_outs": time_outs, "fall_rate": _ratio(falls, episodes),
+        "skipped": skipped, "steps": int(steps),
+        "rms_err_vx": rms("err_vx2"), "rms_err_vy": rms("err_vy2"), "rms_err_wz": rms("err_wz2"),
+        "distance_per_episode": _ratio(dist, episodes),
+        "cost_of_transport": _ratio(tot["work_pos"], weight_dist),
+        "slip_per_metre": _ratio(tot["slip"], dist),
+        "tilt_rms": rms("tilt2"),  # RMS of sin(angle between the base z axis and the vertical)
+        "double_support_fraction": _ratio(tot["double_support"], steps),
+        "flight_fraction": _ratio(tot["flight"], steps),
+        "peak_torque_ratio": float(d[N.METRICS_NAMES.index("peak_torque")].max()) if episodes > 0 else None,
+        "mean_torque2": _ratio(tot["torque2"], steps * dt),
+        "action_rate_rms": rms("action_rate2"),
+    }
+
+
+def gait_report_arrays(done, counts, total_mass, gravity, dt, terrain_types=None):
+    """gait_report_row over all envs; with terrain_types ([n] ints) a dict
+    {"overall": row, "terrain_types": {type: row}} with one row per value present."""
+    row = gait_report_row(done, counts, total_mass, gravity, dt)
+    if terrain_types is None:
+        return row
+    d, c = np.asarray(done, np.float64), np.asarray(counts, np.int64)
+    m, t = np.asarray(total_mass, np.float64).reshape(-1), np.asarray(terrain_types).reshape(-1).astype(np.int64)
+    return {"overall": row,
+            "terrain_types": {int(k): gait_report_row(d[:, t == k], c[:, t == k], m[t == k], gravity, dt)
+                              for k in np.unique(t)}}
 
 
 def critic_height_grid(cfg):
@@ -151,6 +208,8 @@ def build_hg_cfg(cfg, num_envs, sim_dt, seed, model_js, heightfield=None, hf_sha
     # command curriculum (update_command_curriculum, humanoid_env.py:1097-1106)
     c.cmd_curriculum = int(bool(getattr(cfg.commands, "curriculum", False)))
     c.cmd_max_curriculum = float(getattr(cfg.commands, "max_curriculum", 0.0))
+    # gait metrics (BUILD-DEFINED, include/hgsim.h hg_cfg.gait_metrics)
+    c.gait_metrics = int(bool(getattr(getattr(cfg, "metrics", None), "gait", False)))
     # per-episode actuator randomisation (BUILD-DEFINED, include/hgsim.h hg_cfg.actuator_rand)
     dr = cfg.domain_rand
     c.actuator_rand = int(bool(getattr(dr, "randomize_actuators", False)))
@@ -516,6 +575,18 @@ class XBotLFreeEnv(BaseTask):
         # latest step, and the env each half-wave runs next (a permutation within every XCD range)
         self.env_rows = self._view(T["ENV_ROWS"])
         self.env_order = self._view(T["ENV_ORDER"])
+        self._gait = bool(self._hgcfg.gait_metrics)
+        if self._gait:
+            # metrics.gait: the accumulators ([13, N] float64 slot sums of the running episode and of
+            # the completed ones, [4, N] int32 episodes / falls / time_outs / skipped) and the public
+            # surface, which exists only with the option on
+            self.metrics_running = self._view(T["METRICS_RUN"])
+            self.metrics_completed = self._view(T["METRICS_DONE"])
+            self.metrics_counts = self._view(T["METRICS_COUNT"])
+            self.metrics_names = list(N.METRICS_NAMES)
+            self.clear_gait_metrics = self._clear_gait_metrics
+            self.gait_report = self._gait_report
+            self.gait_pack = self._gait_pack
 
     def _global_ids(self):
         """(offset, total): this shard's envs are global ids [offset, offset + num_envs) of total."""
@@ -748,10 +819,47 @@ class XBotLFreeEnv(BaseTask):
         N.check(self.hg.hg_set_actuator_props(self.sim, *ptrs, self._stream()), self.sim)
         self._per_env_actuators = True
 
+    # ------------------------------------------------------------------ gait metrics
+    _gait = False  # metrics.gait
+
+    def _clear_gait_metrics(self):
+        """Zero the running rows, the completed rows and the counters (ordered on the current stream)."""
+        N.check(self.hg.hg_metrics_clear(self.sim, self._stream()), self.sim)
+
+    def _gait_pack(self):
+        """[19, N] float64 on the device: the completed rows, the four counters, body_mass and the
+        terrain types (0 on the plane) — everything a report needs, for one device-to-host copy."""
+        tt = getattr(self, "terrain_types", None)
+        tt = torch.zeros(1, self.num_envs, dtype=torch.float64, device=self.device) if tt is None else tt.view(1, -1)
+        return torch.cat([self.metrics_completed, self.metrics_counts.to(torch.float64),
+                          self.body_mass.view(1, -1).to(torch.float64), tt.to(torch.float64)])
+
+    def gait_report_from_packed(self, packed, by_terrain_type=False):
+        """The report from a host copy of gait_pack() (the runner copies it asynchronously)."""
+        a = np.asarray(packed, np.float64)
+        done, counts, base_mass, tt = a[:13], np.rint(a[13:17]).astype(np.int64), a[17], np.rint(a[18]).astype(np.int64)
+        # m_e: the model's link masses with the base's replaced by body_mass[e]; g: what K_step runs with
+        links = float(sum(float(self._model.mass[b]) for b in range(1, self._model.num_bodies)))
+        return gait_report_arrays(done, counts, links + base_mass, abs(float(self._hgcfg.gravity_z)),
+                                  float(self._hgcfg.sim_dt) * int(self._hgcfg.decimation),
+                                  tt if by_terrain_type else None)
+
+    def _gait_report(self, by_terrain_type=False):
+        """Gait figures over the episodes completed since the last clear_gait_metrics(), computed on
+        the host in float64 from one device-to-host copy (a host wait: nothing on the step path
+        calls it): RMS command-tracking errors, distance per episode, cost of transport
+        sum(work_pos) / sum(m_e g distance_e), slip per metre, tilt, support fractions, the peak
+        torque ratio, episodes, the fall rate, skipped samples; None where no episode has completed.
+        by_terrain_type: {"overall": row, "terrain_types": {type: row}}."""
+        return self.gait_report_from_packed(self._gait_pack().cpu().numpy(), by_terrain_type)
+
     def _launch_reset(self, mask_u8):
         mp = ctypes.c_void_p(mask_u8.data_ptr()) if mask_u8 is not None else None
         N.check(self.hg.hg_reset_masked(self.sim, mp, ctypes.c_uint64(self.common_step_counter), self._stream()),
                 self.sim)
+        if self._gait:
+            # a manual reset discards the running episode of the envs it resets: it is not counted
+            N.check(self.hg.hg_metrics_fold(self.sim, 1, mp, self._stream()), self.sim)
         self._publish_extras()
 
     def step(self, actions):
@@ -771,6 +879,14 @@ class XBotLFreeEnv(BaseTask):
                 self.sim)
         if kt is not None:
             kt.stop("k_step")
+        if self._gait:
+            # the physical, pre-reset state of this step and the commands it was driven with
+            if kt is not None:
+                kt.start("k_metrics_sample")
+            N.check(self.hg.hg_metrics_sample(self.sim, s), self.sim)
+            if kt is not None:
+                kt.stop("k_metrics_sample")
+        if kt is not None:
             kt.start("k_post")
         self.common_step_counter += 1
         if self.cfg.terrain.measure_heights:
@@ -787,6 +903,13 @@ class XBotLFreeEnv(BaseTask):
         N.check(self.hg.hg_post(self.sim, ctypes.c_uint64(self.common_step_counter), s), self.sim)
         if kt is not None:
             kt.stop("k_post")
+        if self._gait:
+            # the envs this post launch reset end their episode (fall or time-out)
+            if kt is not None:
+                kt.start("k_metrics_fold")
+            N.check(self.hg.hg_metrics_fold(self.sim, 0, None, s), self.sim)
+            if kt is not None:
+                kt.stop("k_metrics_fold")
         self._publish_extras()
         if self._depth is not None:
             # after the post launch: the pose the observations were written from (post-reset).

@@ -15,6 +15,9 @@ as ``DIR/frame_%05d.png``; when ``cv2`` is importable the frames also go into ``
 ``--record`` play keeps the task's own terrain type instead of forcing the plane, so stairs can be
 filmed.  There is no interactive viewer.
 
+With ``metrics.gait`` on in the task's config play ends by printing env.gait_report (tracking errors,
+cost of transport, slip, fall rate, ...) over the episodes the rollout completed.
+
 Reference defect fixed: play.py:77 sets ``train_cfg.runner.resume = True``, but
 ``make_alg_runner`` resets it to False before reading it (task_registry.py:137), so without an
 explicit ``--resume`` the reference exports and plays the randomly initialised policy.  Here the
@@ -125,6 +128,10 @@ def play(args, steps=100, record=None, record_env=0, record_every=1):
         print(f"Average rewards per second over {n_eps} episodes:")
         for name, v in rew_sums.items():
             print(f" - {name}: {v / n_eps:.4f}")
+    if hasattr(env, "gait_report"):  # metrics.gait: the completed episodes' gait figures
+        from humanoid.scripts.evaluate import format_report
+        print("Gait metrics over the completed episodes:")
+        print(format_report(env.gait_report(by_terrain_type=True)))
     return np.array(actions_log)
 
 

@@ -180,6 +180,13 @@ typedef struct hg_cfg {
    * for the same reason as the actuator fields above.) */
   int32_t critic_heights;               /* P, the number of sample points; 0 = off */
   float critic_height_scale;            /* normalization.obs_scales.height_measurements */
+  /* gait metrics (BUILD-DEFINED: the reference only has Logger.log_rewards; 0 = off, and then nothing
+   * changes: no buffer is laid out, nothing is launched, and the three hg_metrics_* entry points
+   * return HG_ERR_ARG).  != 0: hg_create lays out HG_T_METRICS_RUN / _DONE / _COUNT and the caller
+   * brackets every hg_post with hg_metrics_sample and hg_metrics_fold (below).  The field lays out the
+   * arena: hg_update_cfg refuses a change.  (It fills the four bytes of padding in front of the
+   * pointer below, so no other field moves and sizeof(hg_cfg) stays.) */
+  int32_t gait_metrics;
   const float* critic_height_points;    /* device f32 [P, 2] base-frame sample grid, caller-owned (the
                                          * _init_height_points grid, :314-328, x-major) */
   const float* terrain_origins;         /* device [rows, cols, 3], caller-owned */
@@ -195,7 +202,7 @@ typedef struct hg_cfg {
 
 typedef struct hg_desc {
   size_t offset_bytes;  /* into the arena */
-  int32_t dtype;        /* 0 f32, 1 i64, 2 u8(bool), 3 i32 */
+  int32_t dtype;        /* 0 f32, 1 i64, 2 u8(bool), 3 i32, 4 f64 */
   int32_t ndim;
   int64_t shape[4];
   int64_t strides[4];   /* in elements */
@@ -237,6 +244,12 @@ enum hg_tensor_id {
                             without a copy launch */
   HG_T_ROWS_DROPPED,     /* [N] int32: constraint rows / contact points the row budget dropped, summed over substeps;
                          * zero at hg_create, CUMULATIVE afterwards (resets do not clear it: zero it before a run) */
+  /* the gait-metrics accumulators (hg_cfg.gait_metrics; with it off they have no storage and hg_tensor
+   * refuses them).  They sit here, not at the end: the command curriculum's ids stay the last, and
+   * every caller goes by name. */
+  HG_T_METRICS_RUN,      /* [13,N] f64, SoA strides (np,1): the running episode's slot sums (hg_metrics_sample) */
+  HG_T_METRICS_DONE,     /* [13,N] f64: the slot sums over the env's completed episodes (hg_metrics_fold) */
+  HG_T_METRICS_COUNT,    /* [4,N] int32: completed episodes, falls, time_outs, skipped samples */
   HG_T_ENV_ROWS,         /* [N] int32, read-only diagnostic: constraint rows of each env in the latest hg_step (the
                             wave-balancing sort key) */
   HG_T_ENV_ORDER,        /* [N] int32, read-only diagnostic: the env K_step's half-wave k runs, as the latest post
@@ -292,7 +305,7 @@ int hg_obs_window_advance(void* sim);
 /* Runtime parameter update (curricula, e.g. the push-recovery ramp of config 5): copies *cfg into
  * the handle and, stream-ordered, into the device copy the kernels read.  Fields that size or
  * lay out the arena (num_envs, frame stacks, terrain tables, decimation, critic_heights and its
- * grid pointer) must be unchanged. */
+ * grid pointer, gait_metrics) must be unchanged. */
 int hg_update_cfg(void* sim, const hg_cfg* cfg, void* stream);
 /* replaces reset_idx() (humanoid_env.py:1109-1163) for an explicit device mask [N] (u8). */
 int hg_reset_masked(void* sim, const uint8_t* mask, uint64_t counter, void* stream);
@@ -333,6 +346,56 @@ int hg_set_actuator_props(void* sim, const float* kp_scale, const float* kd_scal
  * clipped to [0, rows-2] x [0, cols-2]) and reads min(h[i][j], h[i+1][j], h[i][j+1]) *
  * vertical_scale.  Zeros on a plane (terrain_type 0), as the reference. */
 int hg_measure_heights(void* sim, const float* points_xy, int num_points, float* out, void* stream);
+
+/* ---- gait metrics per episode (BUILD-DEFINED; replaces the dozen torch ops per step of the
+ * evaluation loop in scripts/sim2sim.py, and gives training runs figures the reward means do not:
+ * the reference only has Logger.log_rewards) ----
+ * Standalone calls like hg_measure_heights: they read the arena, write only the three metrics
+ * buffers, allocate nothing and do not synchronise (capturable).  One thread per env, no atomics.
+ * The caller's step is  hg_step, hg_metrics_sample, hg_post, hg_metrics_fold(mode 0):  the sample
+ * sees the physical, pre-reset state of the step and the commands it was driven with; the fold sees
+ * the reset / time-out flags the post launch left.
+ * hg_metrics_sample adds one sample per env e < N to row e of HG_T_METRICS_RUN.  Every f32 input is
+ * converted to double and all arithmetic is double, without fused multiply-add, sums over joints
+ * j = 0..11 and over the two feet in index order (csrc/hg_metrics_sample.h is the statement):
+ *   dt = (double)sim_dt * decimation, the policy step;
+ *   q = the root quaternion times 1 / its norm (as hg_render_depth normalises it);
+ *   v_b, w_b = the world root linear / angular velocity rotated by the inverse of q, g_b = (0, 0, -1)
+ *   rotated the same way (quat_rotate_inverse's expression);  c = commands[0..2];
+ *   tau = HG_T_TORQUES, qd = HG_T_DOF_VEL;  a, a_prev = HG_T_ACTIONS, HG_T_LAST_ACTIONS as they stand
+ *   before the post launch;  feet = cfg.feet_body[0..1], a foot is in contact when its world
+ *   HG_T_CONTACT_FORCES z is > 5 (strict; contact_mask, humanoid_env.py:833);  v_foot = the foot
+ *   body's world linear velocity in HG_T_RIGID_STATE.
+ *     slot 0  steps           += 1
+ *     slot 1  err_vx2         += (v_b.x - c0)^2
+ *     slot 2  err_vy2         += (v_b.y - c1)^2
+ *     slot 3  err_wz2         += (w_b.z - c2)^2
+ *     slot 4  distance        += sqrt(v_world.x^2 + v_world.y^2) * dt
+ *     slot 5  work_pos        += (sum_j max(tau_j * qd_j, 0)) * dt
+ *     slot 6  torque2         += (sum_j tau_j^2) * dt
+ *     slot 7  tilt2           += g_b.x^2 + g_b.y^2
+ *     slot 8  slip            += (sum over feet in contact of sqrt(v_foot.x^2 + v_foot.y^2)) * dt
+ *     slot 9  action_rate2    += sum_j (a_j - a_prev_j)^2
+ *     slot 10 double_support  += 1 when both feet are in contact
+ *     slot 11 flight          += 1 when neither is
+ *     slot 12 peak_torque      = max(itself, max_j |tau_j| / cfg.torque_limit[j])   (a running max, not a sum)
+ *   If any input the sample reads (root quaternion and velocities, commands[0..2], the four joint
+ *   arrays, the feet's contact z and linear velocity x, y) is non-finite the whole sample is skipped
+ *   and HG_T_METRICS_COUNT[3][e] (skipped) is incremented instead: no row ever holds a NaN.
+ * hg_metrics_fold, mode 0 (episode end): for every env with HG_T_RESET_BUF[e] set, as the latest
+ *   post launch left it, and steps > 0 in its running row: slots 0-11 are added to row e of
+ *   HG_T_METRICS_DONE, slot 12 takes the max, HG_T_METRICS_COUNT[0][e] (episodes) is incremented, then
+ *   [1][e] (falls) when HG_T_TIME_OUT_BUF[e] is 0 and [2][e] (time_outs) otherwise, and the running row
+ *   is zeroed; other envs are untouched.  mode 1 (discard): the running rows of the envs in the device
+ *   u8 mask [N] (NULL = all) are zeroed and nothing is counted — what a manual reset
+ *   (hg_reset_masked) is paired with.  mask is ignored in mode 0.
+ * hg_metrics_clear zeroes all three buffers (stream-ordered).
+ * Columns e >= N of the padded buffers are never written.
+ * HG_ERR_ARG before any launch (hg_last_error names the reason): sim NULL; cfg.gait_metrics == 0 for
+ * this sim; a mode other than 0 / 1. */
+int hg_metrics_sample(void* sim, void* stream);
+int hg_metrics_fold(void* sim, int mode, const uint8_t* mask, void* stream);
+int hg_metrics_clear(void* sim, void* stream);
 
 /* ---- base-mounted depth camera (replaces the camera sensor attach_camera creates,
  * humanoid_env.py:399-423, and its depth image; BUILD-DEFINED: there is no graphics pipeline here,
