@@ -338,3 +338,15 @@ __device__ __forceinline__ void hg_lin16_acc(const float* __restrict__ xr, const
     }
   }
 }
+
+// One 8-deep k group of a 32 x 32 tile on v_mfma_f32_32x32x2_f32 (A[i][k = h], B[k = h][j = i]): lane
+// (i, h) holds the float4 k = 8q + 4h + 0..3 of its A row and its B row, and MFMA s takes component
+// s of both, one accumulator chain.  The k order of hg_gemm.hip's f32 tiles (mma_chunk) and of the
+// rollout's fused 512 -> 256 stage (hg_rollout.hip), which therefore sum in the same order.
+typedef float hg_f32x16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ void hg_mma32_k8(const float4& a, const float4& b, hg_f32x16& acc) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
+}

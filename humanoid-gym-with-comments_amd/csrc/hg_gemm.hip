@@ -166,12 +166,7 @@ __device__ __forceinline__ void mma_chunk(const float* __restrict__ As, const fl
 #pragma unroll
     for (int m = 0; m < TM; m++)
 #pragma unroll
-      for (int n = 0; n < TN; n++) {
-        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m].x, b[n].x, acc[m][n], 0, 0, 0);
-        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m].y, b[n].y, acc[m][n], 0, 0, 0);
-        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m].z, b[n].z, acc[m][n], 0, 0, 0);
-        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m].w, b[n].w, acc[m][n], 0, 0, 0);
-      }
+      for (int n = 0; n < TN; n++) hg_mma32_k8(a[m], b[n], acc[m][n]);  // hg_common.h: shared with k_act_tail2
   }
 }
 
@@ -1588,6 +1583,37 @@ extern "C" int hg_gemm_f32_splitk(const float* A, int64_t lda, const float* B, i
   }
   if (rc != HG_OK) return rc;
   return splitk_finish(ws, bias, C, ldc, M, N, slices, elu, s);
+}
+
+// hg_gemm_f32_splitk's slices alone: the mode-4 launch writes ws [S][M][N] and nothing sums it
+// (the rollout's hg_rollout_act_tail2 does, in the finish's order).  The same checks, kslice and
+// tiles, so the workspace holds the bits hg_gemm_f32_splitk leaves in it.
+extern "C" int hg_gemm_f32_splitk_partials(const float* A, int64_t lda, const float* B, int64_t ldb, float* ws,
+                                           int64_t ws_floats, int64_t M, int N, int K, int tile, int slices,
+                                           void* stream) {
+  if (!A || !B || !ws || M <= 0 || N <= 0 || K <= 0 || lda < K || ldb < K || tile < 20 || tile > 28 || slices < 2 ||
+      slices > 16)
+    return HG_ERR_ARG;
+  const int64_t kslice = hg_gemm_splitk_kslice(K, slices);
+  if ((slices - 1) * kslice >= K) return HG_ERR_ARG;  // every slice holds part of the reduction
+  if (ws_floats < slices * M * (int64_t)N) return HG_ERR_ARG;
+  if ((uintptr_t)A % 4 || (uintptr_t)B % 4 || (uintptr_t)ws % 16) return HG_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  GemmArgs g{A, lda, B, ldb, nullptr, nullptr, 0, ws, N, nullptr, M, N, K, 0, 0};
+  GemmX6Args xa{g, kslice, M * (int64_t)N, slices};
+  const bool vec = lda % 4 == 0 && ldb % 4 == 0 && (uintptr_t)A % 16 == 0 && (uintptr_t)B % 16 == 0;
+  const int md = 4;
+  switch (tile) {
+    case 20: return launch_x6<128, 128, 2, 2, 1>(md, xa, vec, false, s);
+    case 21: return launch_x6<128, 128, 2, 4, 1>(md, xa, vec, false, s);
+    case 22: return launch_x6<128, 64, 2, 2, 1>(md, xa, vec, false, s);
+    case 23: return launch_x6<64, 64, 2, 2, 1>(md, xa, vec, false, s);
+    case 24: return launch_x6<128, 128, 2, 2, 2>(md, xa, vec, false, s);
+    case 25: return launch_x6<256, 128, 4, 2, 1>(md, xa, vec, false, s);
+    case 26: return launch_x6<128, 128, 2, 4, 2>(md, xa, vec, false, s);
+    case 27: return launch_x6<128, 256, 2, 4, 1>(md, xa, vec, false, s);
+    default: return launch_x6<64, 256, 2, 4, 1>(md, xa, vec, false, s);
+  }
 }
 
 // The same split-K forward with W as the operand image hg_gemm_x6_image_jobs builds (trans 0, N

@@ -241,6 +241,151 @@ __global__ void __launch_bounds__(64 * TAIL_WAVES) k_act_tail(ActTail tl, const 
                    cobs_ld, obs_out_ld, obs_out, cobs_out);
 }
 
+// The actor's policy side after its first layer's split-K slices, in the sampling launch
+// (hg_rollout_act_tail2): k_act_tail's geometry (a block of TAIL_WAVES waves owns 16 rows), four
+// stages with one barrier after each and none inside a K loop.
+//   (a) y1 = elu(ws_0 + ws_1 + ws_2 + ws_3 + b1) for the block's 16 x 512 band, every slice load
+//       issued before the first add, as k_splitk_finish<true, 4> (hg_gemm.hip) sums it -> LDS;
+//   (b) y2 = elu(y1 W2^T + b2): wave w owns columns 32 w .. 32 w + 31, one 32 x 32 accumulator on
+//       v_mfma_f32_32x32x2_f32 in the k order of hg_gemm.hip's f32 tiles (hg_mma32_k8 per 8-deep k
+//       group, 32-wide chunks in order).  A comes from the LDS band (lanes i >= 16 repeat rows 0 ..
+//       15; their accumulator rows are dropped), W2 straight from global memory into registers,
+//       T2_PF chunks ahead — no two waves share a W2 row, so no LDS staging and no barrier -> LDS;
+//   (c) k_act_tail's 256 -> 128 stage (hg_lin16_acc) with its x rows in LDS -> LDS;
+//   (d) k_act_tail's head, sampling and slot writes.
+// Bitwise hg_gemm_f32_splitk's finish + hg_gemm_f32 tile 5 + hg_rollout_act_tail; y1 and y2 never
+// leave the chip.  No block waits on another.
+constexpr int T2_N1 = 512, T2_N2 = 256, T2_S = 4, T2_PF = 3;
+struct ActTail2 {
+  const float* ws;  // [T2_S][n][T2_N1] split-K partials of layer 1
+  int64_t sstride;  // n * T2_N1
+  const float* b1;
+  const float* W2;  // [T2_N2][T2_N1]
+  const float* b2;
+  const float* W3;  // [HEAD_K][T2_N2]
+  const float* b3;
+  const float* W;  // [HEAD_N][HEAD_K]
+  const float* b;
+};
+
+template <typename OT>
+__global__ void __launch_bounds__(64 * TAIL_WAVES) k_act_tail2(ActTail2 t2, const float* __restrict__ std,
+                                                               const float* __restrict__ value,
+                                                               const float* __restrict__ obs,
+                                                               const float* __restrict__ cobs, int n, int A,
+                                                               int64_t obs_w, int64_t cobs_w, int64_t obs_ld,
+                                                               int64_t obs_c0, int64_t cobs_ld,
+                                                               float* __restrict__ act_out, float* __restrict__ logp_out,
+                                                               float* __restrict__ mu_out, float* __restrict__ sigma_out,
+                                                               float* __restrict__ value_out, int64_t obs_out_ld,
+                                                               OT* __restrict__ obs_out, OT* __restrict__ cobs_out,
+                                                               int row_offset, uint64_t seed, uint64_t counter,
+                                                               int env_blocks) {
+  static_assert(TAIL_WAVES * 32 == T2_N2 && TAIL_WAVES * 64 * 4 * 4 == 16 * T2_N1, "one block per 16-row band");
+  if ((int)blockIdx.x < env_blocks) {
+    // padded pitches: the 16 rows' float4 reads of one k fall on distinct banks, rows stay 16-byte aligned
+    // hs lies over y1s (dead after (b)'s barrier): 48.5 KB, which every block of the launch reserves,
+    // the copy blocks too — three blocks fit a CU's LDS (two with hs apart; the launch time was the
+    // same, 34.9 against 35.0 us)
+    __shared__ __attribute__((aligned(16))) float lds[16 * (T2_N1 + 4) + 16 * (T2_N2 + 4)];
+    float(*y1s)[T2_N1 + 4] = reinterpret_cast<float(*)[T2_N1 + 4]>(lds);
+    float(*y2s)[T2_N2 + 4] = reinterpret_cast<float(*)[T2_N2 + 4]>(lds + 16 * (T2_N1 + 4));
+    float(*hs)[HEAD_K + 4] = reinterpret_cast<float(*)[HEAD_K + 4]>(lds);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * 16;
+    {  // (a) thread t: columns 4 (t & 127) .. + 3 of rows (t >> 7) + 4 j
+      typedef float fin4 __attribute__((ext_vector_type(4)));
+      const int c0 = 4 * (threadIdx.x & 127), rb = threadIdx.x >> 7;
+      fin4 x[4][T2_S];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const float* p = t2.ws + (int64_t)min((int)r0 + rb + 4 * j, n - 1) * T2_N1 + c0;
+#pragma unroll
+        for (int s = 0; s < T2_S; s++)
+          x[j][s] = __builtin_nontemporal_load(reinterpret_cast<const fin4*>(p + s * t2.sstride));
+      }
+      const float4 bb = *reinterpret_cast<const float4*>(t2.b1 + c0);
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+#pragma unroll
+        for (int s = 1; s < T2_S; s++) {
+          x[j][0].x += x[j][s].x; x[j][0].y += x[j][s].y; x[j][0].z += x[j][s].z; x[j][0].w += x[j][s].w;
+        }
+        float v[4] = {x[j][0].x + bb.x, x[j][0].y + bb.y, x[j][0].z + bb.z, x[j][0].w + bb.w};
+#pragma unroll
+        for (int q = 0; q < 4; q++) v[q] = v[q] > 0.f ? v[q] : expm1f(v[q]);
+        *reinterpret_cast<float4*>(&y1s[rb + 4 * j][c0]) = make_float4(v[0], v[1], v[2], v[3]);
+      }
+    }
+    __syncthreads();
+    {  // (b) lane (i, h): W2 row 32 wv + i, A row i & 15, the float4 k = 32 c + 8 q + 4 h + 0..3
+      const int i = lane & 31, h = lane >> 5;
+      const int col = 32 * wv + i;
+      const float* __restrict__ wp = t2.W2 + (int64_t)col * T2_N1 + 4 * h;
+      const float* ap = &y1s[i & 15][4 * h];
+      constexpr int NC = T2_N1 / 32, NB = T2_PF + 1;
+      float4 bw[NB][4];
+#pragma unroll
+      for (int c = 0; c < T2_PF; c++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) bw[c][q] = *reinterpret_cast<const float4*>(wp + 32 * c + 8 * q);
+      hg_f32x16 acc = (hg_f32x16)0.f;
+      // unrolled: the ring's registers are static, and the scheduling barriers keep each chunk's
+      // loads where they are written (issued T2_PF chunks before their MFMAs)
+#pragma unroll
+      for (int c = 0; c < NC; c++) {
+        if (c + T2_PF < NC) {
+#pragma unroll
+          for (int q = 0; q < 4; q++)
+            bw[(c + T2_PF) % NB][q] = *reinterpret_cast<const float4*>(wp + 32 * (c + T2_PF) + 8 * q);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const float4 a = *reinterpret_cast<const float4*>(ap + 32 * c + 8 * q);
+          hg_mma32_k8(a, bw[c % NB][q], acc);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      const float bc = t2.b2[col];
+#pragma unroll
+      for (int q = 0; q < 8; q++) {  // accumulator register q: row (q & 3) + 8 (q >> 2) + 4 h (epi_forward's map)
+        float v = acc[q] + bc;
+        v = v > 0.f ? v : expm1f(v);
+        y2s[(q & 3) + 8 * (q >> 2) + 4 * h][col] = v;
+      }
+    }
+    __syncthreads();
+    const int i = lane & 15, g = lane >> 4;
+    const int c = wv * 16 + i;
+    {  // (c)
+      const float* xr = &y2s[i][8 * g];
+      const float* wr = t2.W3 + (int64_t)c * T2_N2 + 8 * g;
+      hg_f32x4 acc0, acc1;
+      hg_lin16_acc<true>(xr, wr, T2_N2, g, acc0, acc1);
+      const float bc = t2.b3[c];
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        float v = acc0[q] + acc1[q] + bc;
+        v = v > 0.f ? v : expm1f(v);
+        hs[4 * g + q][c] = v;
+      }
+    }
+    __syncthreads();
+    // (d)
+    if (threadIdx.x >= 16 * ACT_LANES) return;
+    const int el = threadIdx.x / ACT_LANES, j = threadIdx.x % ACT_LANES;
+    const int e = (int)r0 + el;
+    if (e >= n) return;  // whole groups leave together
+    const float m = act_head_mean(&hs[el][0], t2.W, t2.b, j);
+    act_env16(e, j, A, m, std, value, act_out, logp_out, mu_out, sigma_out, value_out, row_offset, seed, counter);
+    return;
+  }
+  act_copy_obs<OT>((int64_t)(blockIdx.x - env_blocks) * TAIL_WAVES + (threadIdx.x >> 6),
+                   (int64_t)(gridDim.x - env_blocks) * TAIL_WAVES, obs, cobs, n, obs_w, cobs_w, obs_ld, obs_c0,
+                   cobs_ld, obs_out_ld, obs_out, cobs_out);
+}
+
 __global__ void __launch_bounds__(TPB) k_env(const float* __restrict__ rew, const uint8_t* __restrict__ reset,
                                             const uint8_t* __restrict__ time_out, const float* __restrict__ values,
                                             int n, float gamma, float* __restrict__ rew_out,
@@ -313,6 +458,32 @@ int launch_act_tail(ActTail tl, const float* std, const float* value, const floa
 #undef HG_ACTT
   return hipGetLastError() == hipSuccess ? HG_OK : HG_ERR_HIP;
 }
+
+int launch_act_tail2(ActTail2 t2, const float* std, const float* value, const float* obs, const float* critic_obs,
+                     int num_envs, int num_actions, int64_t obs_width, int64_t critic_obs_width, int64_t obs_ld,
+                     int64_t obs_col0, int64_t critic_obs_ld, float* actions_out, float* logp_out, float* mu_out,
+                     float* sigma_out, float* value_out, void* obs_out, int64_t obs_out_ld, void* critic_obs_out,
+                     int obs_fp16, int row_offset, uint64_t seed, uint64_t counter, void* stream) {
+  if (!std || (value && !value_out) || !obs || !actions_out || !logp_out || !mu_out || !sigma_out || !obs_out ||
+      num_envs <= 0 || num_actions != HEAD_N || obs_width <= 0 || obs_col0 < 0 ||
+      (obs_out_ld != 0 && obs_out_ld < obs_width) || obs_ld < obs_col0 + obs_width ||
+      (critic_obs_width > 0 && (!critic_obs || !critic_obs_out || critic_obs_ld < critic_obs_width)))
+    return HG_ERR_ARG;
+  const int env_blocks = (num_envs + 15) / 16;  // k_act_tail's grid
+  const int64_t copy_rows = critic_obs_width > 0 ? 2 * (int64_t)num_envs : num_envs;
+  const int copy_blocks = (int)std::min<int64_t>((copy_rows + TAIL_WAVES - 1) / TAIL_WAVES, 1024);
+  const int64_t cw = critic_obs_width > 0 ? critic_obs_width : 0;
+  const int64_t old = obs_out_ld ? obs_out_ld : obs_width;
+  hipStream_t s = (hipStream_t)stream;
+#define HG_ACTT2(OT) hipLaunchKernelGGL((k_act_tail2<OT>), dim3(env_blocks + copy_blocks), dim3(64 * TAIL_WAVES), 0, s, t2, \
+                                        std, value, obs, critic_obs, num_envs, num_actions, obs_width, cw, obs_ld,         \
+                                        obs_col0, critic_obs_ld, actions_out, logp_out, mu_out, sigma_out, value_out, old,  \
+                                        (OT*)obs_out, (OT*)critic_obs_out, row_offset, seed, counter, env_blocks)
+  if (obs_fp16) HG_ACTT2(__half);
+  else HG_ACTT2(float);
+#undef HG_ACTT2
+  return hipGetLastError() == hipSuccess ? HG_OK : HG_ERR_HIP;
+}
 }  // namespace
 
 extern "C" int hg_rollout_act(const float* mean, const float* std, const float* value, const float* obs,
@@ -362,6 +533,30 @@ extern "C" int hg_rollout_act_tail(const float* x, int64_t x_ld, const float* W3
                          obs_width, critic_obs_width, obs_ld, obs_col0, critic_obs_ld, actions_out, logp_out, mu_out,
                          sigma_out, value_out, obs_out, obs_out_ld, critic_obs_out, obs_fp16, row_offset, seed, counter,
                          stream);
+}
+
+// hg_rollout_act_tail with the actor's first layer's split-K finish and its 512 -> 256 layer folded
+// in too (k_act_tail2): ws [4][num_envs, 512] are hg_gemm_f32_splitk_partials' slices of the first
+// layer (dense, ws_floats >= 4 num_envs 512), b1 its bias, W2 [256, 512] / b2 and W3 [128, 256] / b3
+// the two layers above it (ELU each), W / b the output layer.  Bitwise hg_gemm_f32_splitk's finishing
+// launch, hg_gemm_f32 (mode 0, tile 5) and hg_rollout_act_tail.  16-byte aligned ws, b1, W2, W3, W.
+extern "C" int hg_rollout_act_tail2(const float* ws, int64_t ws_floats, int slices, const float* b1, const float* W2,
+                                    const float* b2, int n1, int n2, const float* W3, const float* b3, const float* W,
+                                    const float* b, const float* std, const float* value, const float* obs,
+                                    const float* critic_obs, int num_envs, int num_actions, int64_t obs_width,
+                                    int64_t critic_obs_width, int64_t obs_ld, int64_t obs_col0, int64_t critic_obs_ld,
+                                    float* actions_out, float* logp_out, float* mu_out, float* sigma_out,
+                                    float* value_out, void* obs_out, int64_t obs_out_ld, void* critic_obs_out,
+                                    int obs_fp16, int row_offset, uint64_t seed, uint64_t counter, void* stream) {
+  if (!ws || !b1 || !W2 || !b2 || !W3 || !b3 || !W || !b || slices != T2_S || n1 != T2_N1 || n2 != T2_N2 ||
+      num_envs <= 0 || ws_floats < (int64_t)T2_S * num_envs * T2_N1 || (uintptr_t)ws % 16 != 0 ||
+      (uintptr_t)b1 % 16 != 0 || (uintptr_t)W2 % 16 != 0 || (uintptr_t)W3 % 16 != 0 || (uintptr_t)W % 16 != 0 ||
+      (uintptr_t)b2 % 4 != 0 || (uintptr_t)b3 % 4 != 0 || (uintptr_t)b % 4 != 0)
+    return HG_ERR_ARG;
+  return launch_act_tail2(ActTail2{ws, (int64_t)num_envs * T2_N1, b1, W2, b2, W3, b3, W, b}, std, value, obs,
+                          critic_obs, num_envs, num_actions, obs_width, critic_obs_width, obs_ld, obs_col0,
+                          critic_obs_ld, actions_out, logp_out, mu_out, sigma_out, value_out, obs_out, obs_out_ld,
+                          critic_obs_out, obs_fp16, row_offset, seed, counter, stream);
 }
 extern "C" int hg_rollout_env(const float* rewards, const uint8_t* reset, const uint8_t* time_outs,
                               const float* values, int num_envs, float gamma, float* rewards_out,

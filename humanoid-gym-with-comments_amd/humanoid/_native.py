@@ -203,14 +203,14 @@ EXPORTS = ["hg_arena_bytes", "hg_create", "hg_destroy", "hg_last_error", "hg_ten
            "hg_set_command_range_x", "hg_publish_terrain_level", "hg_set_dof_state_indexed", "hg_set_root_state_indexed",
            "hg_set_root_state", "hg_set_env_props", "hg_set_actuator_props",
            "hg_measure_heights", "hg_metrics_sample", "hg_metrics_fold", "hg_metrics_clear", "hg_render_depth", "hg_view_shapes", "hg_render_view", "hg_gae_scan", "hg_gae_stats_len", "hg_gae_normalize", "hg_adam_step", "hg_adam_chunk", "hg_kl_mean", "hg_kl_lr_rule",
-           "hg_rollout_act", "hg_rollout_act_head", "hg_rollout_act_tail", "hg_rollout_env", "hg_gather_rows", "hg_gather_rows_ex", "hg_gather_stacked", "hg_ppo_loss", "hg_ppo_loss_lr", "hg_ppo_loss_scratch", "hg_ppo_loss_backward",
+           "hg_rollout_act", "hg_rollout_act_head", "hg_rollout_act_tail", "hg_rollout_act_tail2", "hg_rollout_env", "hg_gather_rows", "hg_gather_rows_ex", "hg_gather_stacked", "hg_ppo_loss", "hg_ppo_loss_lr", "hg_ppo_loss_scratch", "hg_ppo_loss_backward",
            "hg_mirror_rows", "hg_sym_loss", "hg_sym_loss_scratch", "hg_sym_loss_backward",
            "hg_mlp_act_backward", "hg_mlp_act_backward_scratch", "hg_colsum_jobs", "hg_linear_skinny_supported",
            "hg_linear_skinny_forward", "hg_linear_skinny_backward", "hg_linear_skinny_backward_scratch",
            "hg_mlp_act_backward_bf16", "hg_linear_skinny_forward_bf16", "hg_linear_skinny_backward_bf16",
            "hg_cast_bf16_jobs", "hg_linear_act_forward", "hg_linear_act_tile", "hg_gemm_f32", "hg_gemm_tile",
            "hg_gemm_colpart_rows", "hg_gemm_f32_wgrad", "hg_gemm_x6_image_bytes", "hg_gemm_x6_image_jobs", "hg_gemm_x6_image_jobs_pitched", "hg_gemm_wgrad_img",
-           "hg_gemm_f32_img", "hg_gemm_f32_img_split", "hg_gemm_splitk_kslice", "hg_gemm_f32_splitk", "hg_gemm_f32_splitk_img", "hg_linear_skinny_backward_act", "hg_linear_skinny_colpart_rows", "hg_version",
+           "hg_gemm_f32_img", "hg_gemm_f32_img_split", "hg_gemm_splitk_kslice", "hg_gemm_f32_splitk", "hg_gemm_f32_splitk_partials", "hg_gemm_f32_splitk_img", "hg_linear_skinny_backward_act", "hg_linear_skinny_colpart_rows", "hg_version",
            "hg_source_hash"]
 
 _LIB = None
@@ -327,6 +327,9 @@ def load_library(path=LIB_PATH):
     L.hg_rollout_act_head.argtypes = [vp, ctypes.c_int64, vp, vp, ctypes.c_int] + L.hg_rollout_act.argtypes[1:]
     L.hg_rollout_act_tail.restype = ctypes.c_int
     L.hg_rollout_act_tail.argtypes = [vp, ctypes.c_int64, vp, vp, ctypes.c_int, vp, vp] + L.hg_rollout_act.argtypes[1:]
+    L.hg_rollout_act_tail2.restype = ctypes.c_int
+    L.hg_rollout_act_tail2.argtypes = [vp, ctypes.c_int64, ctypes.c_int, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp,
+                                       vp, vp] + L.hg_rollout_act.argtypes[1:]
     L.hg_gather_stacked.restype = ctypes.c_int
     L.hg_gather_stacked.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                     ctypes.c_int, ctypes.c_int,
@@ -426,6 +429,9 @@ def load_library(path=LIB_PATH):
     L.hg_gemm_f32_splitk.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, ctypes.c_int64,
                                      ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      vp]
+    L.hg_gemm_f32_splitk_partials.restype = ctypes.c_int
+    L.hg_gemm_f32_splitk_partials.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
     L.hg_gemm_f32_splitk_img.restype = ctypes.c_int
     L.hg_gemm_f32_splitk_img.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp,
                                          ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,

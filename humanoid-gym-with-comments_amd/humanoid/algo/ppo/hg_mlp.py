@@ -827,6 +827,54 @@ def mlp_infer_tail(net, x):
     return h, W, b
 
 
+# the first layer's split-K finish and the 512 -> 256 layer folded into that launch too
+# (hg_rollout_act_tail2): the sampling launch then reads the first layer's split-K slices
+TAIL2_FUSED = os.environ.get("HG_ACT_TAIL2", "1") != "0"
+
+
+def mlp_infer_tail2(net, x):
+    """For hg_rollout_act_tail2: the split-K slices of ``net``'s first layer (no finishing launch)
+    and the three layers above it -> (ws, slices, b1, W2, b2, W3, b3); None (nothing computed)
+    unless mlp_infer_tail would apply, the net is K1 -> 512 -> 256 -> 128 -> out, the first layer's
+    route is the 4-slice split-K of ``_GEMM_FWD_SPLITK``, the second's an f32 k_gemm tile of
+    ``_GEMM_FWD`` (every f32 tile sums a 512-deep row in one order), every pointer the launch reads
+    as float4 is 16-byte aligned, and the tail and the head are fused — so the launch gives the
+    three separate launches' bits."""
+    from . import ppo  # HEAD_FUSED lives with the caller (ppo imports this module)
+    if not (TAIL2_FUSED and TAIL_FUSED and ppo.HEAD_FUSED and fusable(net)):
+        return None
+    mods = list(net)
+    if len(mods) != 7:
+        return None
+    (W1, b1), (W2, b2), (W3, b3) = ((mods[j].weight, mods[j].bias) for j in (0, 2, 4))
+    rows = x.shape[0]
+    if (W1.device != x.device or not x.is_cuda or x.dim() != 2 or x.dtype != torch.float32
+            or W1.shape[0] != 512 or tuple(W2.shape) != (256, 512) or tuple(W3.shape) != (128, 256)):
+        return None
+    # the tail's own conditions (mlp_infer_tail) on the 256 -> 128 layer
+    if (not W3.is_contiguous() or W3.data_ptr() % 16 or not b3.is_contiguous()
+            or _route(_GEMM_FWD, rows, 256, 128) or (256, 128) in _GEMM_FWD_SPLITK or not FUSED_FORWARD
+            or rows > _FUSED_FWD_ROWS.get((256, 128), 0) or int(N.lib().hg_linear_act_tile(rows, 128, 256)) != 5):
+        return None
+    # layer 1: 4 split-K slices; layer 2: not split, an f32 tile
+    split = _gemm_fwd_splitk(x, W1, b1)
+    if split is None or split[1] != 4 or not 20 <= split[0] <= 28:
+        return None
+    if (not (W2.is_contiguous() and b2.is_contiguous()) or (512, 256) in _GEMM_FWD_SPLITK
+            or not 0 < _route(_GEMM_FWD, rows, 512, 256) < X6_TILE0):
+        return None
+    if b1.data_ptr() % 16 or W2.data_ptr() % 16:
+        return None
+    tile, slices = split
+    k = W1.shape[1]
+    ws = torch.empty(slices * rows * 512, dtype=torch.float32, device=x.device)
+    rc = N.lib().hg_gemm_f32_splitk_partials(x.data_ptr(), x.stride(0), W1.data_ptr(), W1.stride(0), ws.data_ptr(),
+                                             ws.numel(), rows, 512, k, tile, slices, _stream(x.device))
+    if rc != 0:
+        raise RuntimeError(f"hg_gemm_f32_splitk_partials failed ({rc})")
+    return ws, slices, b1, W2, b2, W3, b3
+
+
 def head_fusable(h, W):
     """The output layer W applied to h can run inside hg_rollout_act_head (12 x 128, aligned rows)."""
     return (h is not None and tuple(W.shape) == (12, 128) and W.is_contiguous() and h.dim() == 2

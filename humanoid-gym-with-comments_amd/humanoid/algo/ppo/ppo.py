@@ -273,15 +273,20 @@ class PPO:
         t = st.step
         # the actor's output layer runs inside the sampling launch when it is the 12 x 128 head
         # (hg_rollout_act_head: bitwise the separate output-layer launch); the mean lands in mu
-        mean = head = tail = None
+        mean = head = tail = tail2 = None
         last = ac.actor[-1]
         if (HEAD_FUSED and ac.policy_dtype == "fp32" and ac.fused_mlp and not torch.is_grad_enabled()
                 and isinstance(last, torch.nn.Linear) and tuple(last.weight.shape) == (12, 128)
                 and last.bias is not None and last.bias.is_contiguous() and hg_mlp.fusable(ac.actor)):
-            # the last hidden layer too when its route allows (hg_rollout_act_tail), else the head only
+            # everything above the first layer's split-K slices when the routes allow
+            # (hg_rollout_act_tail2), else the last hidden layer (hg_rollout_act_tail), else the head only
             if last.weight.is_contiguous() and last.weight.data_ptr() % 16 == 0:
-                tail = hg_mlp.mlp_infer_tail(ac.actor, obs)
-            if tail is not None:
+                tail2 = hg_mlp.mlp_infer_tail2(ac.actor, obs)
+                if tail2 is None:
+                    tail = hg_mlp.mlp_infer_tail(ac.actor, obs)
+            if tail2 is not None:
+                head = tail2
+            elif tail is not None:
                 head = tail
             else:
                 h = hg_mlp.mlp_infer_hidden(ac.actor, obs)
@@ -308,7 +313,13 @@ class PPO:
             w, c0 = st.frame_width, obs.shape[1] - st.frame_width
         else:
             w, c0 = obs.shape[1], 0
-        if tail is not None:
+        if tail2 is not None:
+            ws, slices, b1, W2, b2, W3, b3 = tail2
+            W, b = last.weight, last.bias
+            fn = N.lib().hg_rollout_act_tail2
+            lead = (p(ws), ctypes.c_int64(ws.numel()), slices, p(b1), p(W2), p(b2), W2.shape[1], W2.shape[0], p(W3),
+                    p(b3), p(W), p(b), p(std))
+        elif tail is not None:
             x3, W3, b3 = tail
             W, b = last.weight, last.bias
             fn = N.lib().hg_rollout_act_tail

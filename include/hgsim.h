@@ -549,6 +549,23 @@ int hg_rollout_act_tail(const float* x, int64_t x_ld, const float* W3, const flo
                         float* actions_out, float* logp_out, float* mu_out, float* sigma_out, float* value_out,
                         void* obs_out, int64_t obs_out_ld, void* critic_obs_out, int obs_fp16, int row_offset,
                         uint64_t seed, uint64_t counter, void* stream);
+/* hg_rollout_act_tail with two more of the actor's launches folded in (one launch instead of
+ * hg_gemm_f32_splitk's finishing launch + hg_gemm_f32 + hg_rollout_act_tail): ws holds the
+ * `slices` == 4 split-K partials [4][N, n1] of the first hidden layer (hg_gemm_f32_splitk_partials;
+ * ws_floats >= 4 N n1), summed in slice order, + b1, ELU, as that finishing launch does; then
+ * y2 = elu(y1 W2^T + b2), W2 [n2, n1], in the order of hg_gemm_f32's f32 tiles (mode 0, tile 5);
+ * then W3 [128, n2] / b3, the head W [12, 128] / b and the sampling as in hg_rollout_act_tail.
+ * Bitwise those launches' result; y1 and y2 stay on chip.  Supported: n1 == 512, n2 == 256, A == 12,
+ * 16-byte aligned ws / b1 / W2 / W3 / W (else HG_ERR_ARG: run the separate launches).  Replaces the
+ * same span of ActorCritic.act as they do (reference actor_critic.py:53-89, 111-121). */
+int hg_rollout_act_tail2(const float* ws, int64_t ws_floats, int slices, const float* b1, const float* W2,
+                         const float* b2, int n1, int n2, const float* W3, const float* b3, const float* W,
+                         const float* b, const float* std, const float* value, const float* obs,
+                         const float* critic_obs, int num_envs, int num_actions, int64_t obs_width,
+                         int64_t critic_obs_width, int64_t obs_ld, int64_t obs_col0, int64_t critic_obs_ld,
+                         float* actions_out, float* logp_out, float* mu_out, float* sigma_out, float* value_out,
+                         void* obs_out, int64_t obs_out_ld, void* critic_obs_out, int obs_fp16, int row_offset,
+                         uint64_t seed, uint64_t counter, void* stream);
 int hg_rollout_env(const float* rewards, const uint8_t* reset, const uint8_t* time_outs, const float* values,
                    int num_envs, float gamma, float* rewards_out, uint8_t* dones_out, uint8_t* time_outs_out,
                    void* stream);
@@ -858,6 +875,11 @@ int64_t hg_gemm_splitk_kslice(int K, int slices);
 int hg_gemm_f32_splitk(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, float* C,
                        int64_t ldc, float* ws, int64_t ws_floats, int64_t M, int N, int K, int act, int tile,
                        int slices, void* stream);
+/* hg_gemm_f32_splitk's first launch alone: the slices in ws (the same checks, kslice and tiles: the
+ * bits hg_gemm_f32_splitk leaves there), no sum — for a consumer that finishes them itself
+ * (hg_rollout_act_tail2). */
+int hg_gemm_f32_splitk_partials(const float* A, int64_t lda, const float* B, int64_t ldb, float* ws, int64_t ws_floats,
+                                int64_t M, int N, int K, int tile, int slices, void* stream);
 /* hg_gemm_f32_splitk with W as its operand image (Bimg: hg_gemm_x6_image_jobs trans 0 of W [N, K],
  * bimg_bytes = hg_gemm_x6_image_bytes(N, K)): the slices read W's bf16 planes instead of splitting
  * W per block; bitwise the same C as hg_gemm_f32_splitk on the same tile.  Tiles 19..32 except 24,
