@@ -10,6 +10,7 @@
 
 #include "hg_common.h"
 #include "hg_metrics_sample.h"  // HG_METRICS_SLOTS / HG_METRICS_COUNTS
+#include "hg_stride_sample.h"   // HG_STRIDE_SLOTS / HG_STRIDE_STATE_SLOTS
 
 extern "C" int hg_launch_step(const HgState* S, const hg_cfg* hcfg, const float* actions, uint64_t step_counter,
                                int per_env_actuators, hipStream_t stream);
@@ -28,6 +29,9 @@ extern "C" int hg_launch_view(const HgState* S, const hg_cfg* hcfg, const hg_vie
 extern "C" int hg_launch_metrics_sample(const HgState* S, const HgMetrics* M, double dt, hipStream_t stream);
 extern "C" int hg_launch_metrics_fold(const HgState* S, const HgMetrics* M, int mode, const uint8_t* mask,
                                       hipStream_t stream);
+extern "C" int hg_launch_stride_sample(const HgState* S, const HgStride* R, double dt, hipStream_t stream);
+extern "C" int hg_launch_stride_fold(const HgState* S, const HgStride* R, int mode, const uint8_t* mask,
+                                     hipStream_t stream);
 
 namespace {
 
@@ -80,10 +84,15 @@ int dtype_of(int id) {
     case HG_T_EPISODE_LENGTH: return 1;
     case HG_T_NONFINITE: case HG_T_TERRAIN_LEVEL: case HG_T_TERRAIN_TYPE: case HG_T_ROWS_DROPPED:
     case HG_T_ENV_ROWS: case HG_T_ENV_ORDER: case HG_T_METRICS_COUNT: return 3;
-    case HG_T_METRICS_RUN: case HG_T_METRICS_DONE: return 4;
+    case HG_T_METRICS_RUN: case HG_T_METRICS_DONE: case HG_T_STRIDE_RUN: case HG_T_STRIDE_DONE:
+    case HG_T_STRIDE_STATE: return 4;
     default: return 0;
   }
 }
+
+// hg_cfg.gait_metrics is a bit field: bit 0 the per-sample metrics, bit 1 the stride detector (needs bit 0)
+bool strides_on(const hg_cfg* c) { return (c->gait_metrics & 2) != 0; }
+int stride_rows(int id) { return 2 * (id == HG_T_STRIDE_STATE ? HG_STRIDE_STATE_SLOTS : HG_STRIDE_SLOTS); }
 
 // Observation histories as sliding windows: env row e holds F - 1 + HW frame slots; the current
 // stack (the policy input) is slots [head, head + F), head advancing by one per post launch, so a
@@ -118,6 +127,11 @@ Layout make_layout(const hg_cfg* c) {
         o += align256((size_t)(id == HG_T_METRICS_COUNT ? HG_METRICS_COUNTS : HG_METRICS_SLOTS) * np * esize(dtype_of(id)));
       continue;
     }
+    // the stride buffers exist only with bit 1 of cfg.gait_metrics: without it the layout is what it was
+    if (id == HG_T_STRIDE_RUN || id == HG_T_STRIDE_DONE || id == HG_T_STRIDE_STATE) {
+      if (strides_on(c)) o += align256((size_t)stride_rows(id) * np * sizeof(double));
+      continue;
+    }
     o += align256((size_t)soa_rows(id) * np * esize(dtype_of(id)));
   }
   // the observation histories: one sliding window per env row (hg_obs_window_frames)
@@ -150,6 +164,7 @@ struct Sim {
   Layout L;
   HgState S;
   HgMetrics M{nullptr, nullptr, nullptr};  // hg_cfg.gait_metrics: the accumulators (NULL: off)
+  HgStride R{nullptr, nullptr, nullptr};   // hg_cfg.gait_metrics bit 1: the stride buffers (NULL: off)
   int head;    // first window slot of the current observation stack
   uint64_t post_seq = 0;  // post/reset launches so far: EP_STATS ring row of the next one
   int ep_slot = 0;        // ring row written by the latest one
@@ -247,6 +262,8 @@ int hg_create(const hg_cfg* cfg, const hg_model* model, void* arena, size_t aren
     return fail(nullptr, HG_ERR_ARG, "critic_heights must be in [0, HG_MAX_HEIGHT_POINTS (1024)]");
   if (cfg->critic_heights > 0 && !cfg->critic_height_points)
     return fail(nullptr, HG_ERR_ARG, "critic_heights > 0 needs the device sample grid critic_height_points");
+  if (cfg->gait_metrics < 0 || cfg->gait_metrics > 3 || cfg->gait_metrics == 2)
+    return fail(nullptr, HG_ERR_ARG, "gait_metrics must be 0, 1 (metrics) or 3 (metrics and strides): strides (bit 1) need the metrics (bit 0)");
   Sim* s = new Sim();
   s->cfg = *cfg;
   s->model = *model;
@@ -318,6 +335,8 @@ int hg_create(const hg_cfg* cfg, const hg_model* model, void* arena, size_t aren
   S.armature_add = (float*)P(HG_T_ARMATURE_ADD);
   if (cfg->gait_metrics)  // zeroed with the arena below
     s->M = HgMetrics{(double*)P(HG_T_METRICS_RUN), (double*)P(HG_T_METRICS_DONE), (int32_t*)P(HG_T_METRICS_COUNT)};
+  if (strides_on(cfg))
+    s->R = HgStride{(double*)P(HG_T_STRIDE_STATE), (double*)P(HG_T_STRIDE_RUN), (double*)P(HG_T_STRIDE_DONE)};
   {
     // K_step's wave balancing (hg_common.h hg_env_order_block, run by the post launch): on unless HG_WAVE_BALANCE=0
     const char* wb = getenv("HG_WAVE_BALANCE");
@@ -388,6 +407,11 @@ int hg_tensor(void* sim, int id, hg_desc* d) {
     case HG_T_METRICS_RUN: case HG_T_METRICS_DONE: case HG_T_METRICS_COUNT:
       if (!s->cfg.gait_metrics) return fail(s, HG_ERR_ARG, "hg_tensor: gait metrics are off for this sim (hg_cfg.gait_metrics)");
       d->ndim = 2; d->shape[0] = id == HG_T_METRICS_COUNT ? HG_METRICS_COUNTS : HG_METRICS_SLOTS; d->shape[1] = n;
+      d->strides[0] = np; d->strides[1] = 1;
+      return HG_OK;
+    case HG_T_STRIDE_RUN: case HG_T_STRIDE_DONE: case HG_T_STRIDE_STATE:
+      if (!strides_on(&s->cfg)) return fail(s, HG_ERR_ARG, "hg_tensor: stride statistics are off for this sim (hg_cfg.gait_metrics bit 1)");
+      d->ndim = 2; d->shape[0] = stride_rows(id); d->shape[1] = n;
       d->strides[0] = np; d->strides[1] = 1;
       return HG_OK;
     case HG_T_EPISODE_SUMS:
@@ -487,7 +511,7 @@ int hg_update_cfg(void* sim, const hg_cfg* cfg, void* stream) {
       cfg->hf_cols != o.hf_cols || cfg->heightfield != o.heightfield || cfg->terrain_origins != o.terrain_origins ||
       cfg->terrain_rows != o.terrain_rows || cfg->terrain_cols != o.terrain_cols ||
       cfg->critic_heights != o.critic_heights || cfg->critic_height_points != o.critic_height_points ||
-      (cfg->gait_metrics != 0) != (o.gait_metrics != 0))
+      cfg->gait_metrics != o.gait_metrics)
     return fail(s, HG_ERR_ARG, "hg_update_cfg: layout fields cannot change after hg_create");
   if (cfg->pgs_iterations < 0 || cfg->pgs_iterations > 1000 || !(cfg->sim_dt > 0.f))
     return fail(s, HG_ERR_ARG, "hg_update_cfg: bad solver parameters");
@@ -607,6 +631,8 @@ extern "C" int hg_metrics_sample(void* sim, void* stream) {
   const double dt = (double)s->cfg.sim_dt * (double)s->cfg.decimation;  // the policy step
   if (hg_launch_metrics_sample(&s->S, &s->M, dt, (hipStream_t)stream) != 0)
     return fail(s, HG_ERR_HIP, "k_metrics_sample launch failed");
+  if (strides_on(&s->cfg) && hg_launch_stride_sample(&s->S, &s->R, dt, (hipStream_t)stream) != 0)
+    return fail(s, HG_ERR_HIP, "k_stride_sample launch failed");
   return HG_OK;
 }
 
@@ -616,15 +642,20 @@ extern "C" int hg_metrics_fold(void* sim, int mode, const uint8_t* mask, void* s
   if (mode != 0 && mode != 1) return fail(s, HG_ERR_ARG, "hg_metrics_fold: mode must be 0 (episode end) or 1 (discard)");
   if (hg_launch_metrics_fold(&s->S, &s->M, mode, mode == 1 ? mask : nullptr, (hipStream_t)stream) != 0)
     return fail(s, HG_ERR_HIP, "k_metrics_fold launch failed");
+  if (strides_on(&s->cfg) && hg_launch_stride_fold(&s->S, &s->R, mode, mode == 1 ? mask : nullptr, (hipStream_t)stream) != 0)
+    return fail(s, HG_ERR_HIP, "k_stride_fold launch failed");
   return HG_OK;
 }
 
 extern "C" int hg_metrics_clear(void* sim, void* stream) {
   Sim* s = metrics_sim(sim, "hg_metrics_clear");
   if (!s) return HG_ERR_ARG;
-  // the three regions are neighbours in the arena (make_layout): one memset from the first to the arena's next region
+  // the three regions are neighbours in the arena (make_layout), and with bit 1 the three stride
+  // regions follow them: one memset from the first to the arena's next region
   const size_t lo = s->L.off[HG_T_METRICS_RUN];
-  const size_t hi = s->L.off[HG_T_METRICS_COUNT] + align256((size_t)HG_METRICS_COUNTS * s->S.np * sizeof(int32_t));
+  const size_t hi = strides_on(&s->cfg)
+      ? s->L.off[HG_T_STRIDE_STATE] + align256((size_t)stride_rows(HG_T_STRIDE_STATE) * s->S.np * sizeof(double))
+      : s->L.off[HG_T_METRICS_COUNT] + align256((size_t)HG_METRICS_COUNTS * s->S.np * sizeof(int32_t));
   if (hipMemsetAsync(s->arena + lo, 0, hi - lo, (hipStream_t)stream) != hipSuccess)
     return fail(s, HG_ERR_HIP, "hg_metrics_clear: memset failed");
   return HG_OK;

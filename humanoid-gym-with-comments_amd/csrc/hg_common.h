@@ -82,6 +82,14 @@ struct HgMetrics {
   int32_t* count;  // [4][np]  HG_T_METRICS_COUNT: episodes, falls, time_outs, skipped
 };
 
+// the stride detector's buffers (hg_cfg.gait_metrics bit 1, hg_stride.hip), SoA with the arena's
+// stride np, foot-major; held by the sim like HgMetrics
+struct HgStride {
+  double* state;  // [2*8][np]  HG_T_STRIDE_STATE: each foot's phase, counters, anchor, ref / apex height
+  double* run;    // [2*10][np] HG_T_STRIDE_RUN: the running episode's per-foot sums
+  double* done;   // [2*10][np] HG_T_STRIDE_DONE: sums over the completed episodes
+};
+
 // what the statistics block of the post launch needs for the command curriculum and the curriculum
 // extras (hg_envlogic.hip); ring == NULL: neither is on, the block does what it did without them
 struct HgCurriculum {

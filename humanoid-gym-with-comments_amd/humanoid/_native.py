@@ -185,7 +185,8 @@ TENSOR_IDS = [
     "FEET_AIR_TIME", "LAST_CONTACTS", "FEET_HEIGHT", "LAST_FEET_Z", "ENV_FRICTION", "BODY_MASS",
     "PUSH_FORCE", "PUSH_TORQUE", "BASE_LIN_VEL", "BASE_ANG_VEL", "PROJ_GRAVITY", "BASE_EULER",
     "REF_DOF_POS", "ENV_ORIGINS", "EP_STATS", "CONTACT_LAMBDA", "NONFINITE", "TERRAIN_LEVEL", "TERRAIN_TYPE",
-    "EP_STATS_RING", "ROWS_DROPPED", "METRICS_RUN", "METRICS_DONE", "METRICS_COUNT", "ENV_ROWS", "ENV_ORDER",
+    "EP_STATS_RING", "ROWS_DROPPED", "METRICS_RUN", "METRICS_DONE", "METRICS_COUNT",
+    "STRIDE_RUN", "STRIDE_DONE", "STRIDE_STATE", "ENV_ROWS", "ENV_ORDER",
     "KP_SCALE", "KD_SCALE", "ARMATURE_ADD", "CMD_RANGE_X", "CURRICULUM_RING",
 ]
 EP_RING = 64  # HG_EP_RING
@@ -196,6 +197,11 @@ T = {name: i for i, name in enumerate(TENSOR_IDS)}
 METRICS_NAMES = ["steps", "err_vx2", "err_vy2", "err_wz2", "distance", "work_pos", "torque2", "tilt2", "slip",
                  "action_rate2", "double_support", "flight", "peak_torque"]
 METRICS_COUNT_NAMES = ["episodes", "falls", "time_outs", "skipped"]
+# stride statistics (hg_cfg.gait_metrics bit 1): the per-foot slots of HG_T_STRIDE_RUN / _DONE (row
+# f * 10 + k) and of HG_T_STRIDE_STATE (row f * 8 + k)
+STRIDE_NAMES = ["strides", "swing_time", "clearance", "step_length", "step_width", "touchdown_force", "stride_pairs",
+                "stride_length", "stride_time", "short_swings"]
+STRIDE_STATE_NAMES = ["phase", "phase_steps", "since_td", "has_anchor", "anchor_x", "anchor_y", "ref_hag", "apex_hag"]
 
 # every symbol include/hgsim.h declares (checked by tests/test_boundary.py)
 EXPORTS = ["hg_arena_bytes", "hg_create", "hg_destroy", "hg_last_error", "hg_tensor", "hg_step",
@@ -226,14 +232,15 @@ class GatherTable(ctypes.Structure):
 
 def source_hash(pkg_root=PKG_ROOT):
     """sha256 (first 16 hex digits) of the library's sources in the Makefile's stamp order (SRCS,
-    csrc/hg_common.h, csrc/hg_view_shapes.h, csrc/hg_metrics_sample.h, include/hgsim.h), as the Makefile computes it; None when the sources are
+    csrc/hg_common.h, csrc/hg_view_shapes.h, csrc/hg_metrics_sample.h, csrc/hg_stride_sample.h, include/hgsim.h), as the Makefile computes it; None when the sources are
     not in the tree."""
     import hashlib
     try:
         with open(os.path.join(pkg_root, "Makefile")) as f:
             srcs = next(ln.split("=", 1)[1].split() for ln in f if ln.startswith("SRCS ="))
         h = hashlib.sha256()
-        for rel in srcs + ["csrc/hg_common.h", "csrc/hg_view_shapes.h", "csrc/hg_metrics_sample.h", "../include/hgsim.h"]:
+        for rel in srcs + ["csrc/hg_common.h", "csrc/hg_view_shapes.h", "csrc/hg_metrics_sample.h", "csrc/hg_stride_sample.h",
+                           "../include/hgsim.h"]:
             with open(os.path.join(pkg_root, rel), "rb") as f:
                 h.update(f.read())
         return h.hexdigest()[:16]

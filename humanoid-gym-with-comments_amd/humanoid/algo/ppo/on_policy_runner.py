@@ -13,6 +13,8 @@ into last_iteration_stats as gait_<name> and, with a log writer, into Gait/<name
 completed-episode accumulators are cleared behind the read, so each entry covers its own iteration.
 The read rides on the host waits the runner already has (the lazy path copies the accumulators to
 pinned memory behind the update and reads them one iteration later, like the loss means).
+With metrics.strides as well (env.stride_report) the `both` row of the stride figures rides on the
+same copy: stride_<name> in last_iteration_stats, Gait/stride_<name> scalars.
 """
 import json
 import os
@@ -227,8 +229,12 @@ class OnPolicyRunner:
             if hasattr(self.env, "gait_report"):
                 # after the update's own host wait: the iteration's completed episodes, then a fresh interval
                 gait = self.env.gait_report()
+                strides = self.env.stride_report()["both"] if hasattr(self.env, "stride_report") else None
                 self.env.clear_gait_metrics()
                 self._add_gait_stats(gait)
+                if strides is not None:  # only with metrics.strides on; logged as Gait/stride_<name>
+                    self._add_stride_stats(strides)
+                    gait = {**gait, **{"stride_" + k: v for k, v in strides.items()}}
             if self.log_dir is not None:
                 # the rollout's finished episodes in step order, env order within a step (the
                 # order the reference appends them in): one host read per iteration, after the
@@ -252,6 +258,9 @@ class OnPolicyRunner:
     def _add_gait_stats(self, report):
         self.last_iteration_stats.update({"gait_" + k: v for k, v in report.items() if v is not None})
 
+    def _add_stride_stats(self, row):
+        self.last_iteration_stats.update({"stride_" + k: v for k, v in row.items() if v is not None})
+
     def _resolve_stats(self, ev, host_means, copied, gait=None):
         """last_iteration_stats from an iteration's phase events and its loss means (copied to
         pinned host memory behind that iteration's update; waits for that iteration's end only)."""
@@ -267,6 +276,8 @@ class OnPolicyRunner:
         if gait is not None:  # only with metrics.gait on
             gait[1].synchronize()
             self._add_gait_stats(self.env.gait_report_from_packed(gait[0].numpy()))
+            if hasattr(self.env, "stride_report"):  # only with metrics.strides on
+                self._add_stride_stats(self.env.stride_report_from_packed(gait[0].numpy())["both"])
 
     def log(self, locs, width=90, pad=45):
         self.tot_timesteps += self.num_steps_per_env * self.env.num_envs

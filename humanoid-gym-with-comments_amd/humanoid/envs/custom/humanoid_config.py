@@ -119,6 +119,11 @@ class XBotLCfg(BaseConfig):
         # hg_metrics_sample / hg_metrics_fold and env.gait_report() reads the figures; off, nothing
         # of it exists and step() launches what it always did.
         gait = False
+        # stride statistics (BUILD-DEFINED, needs gait): a per-foot detector of lift-off, apex and
+        # touchdown inside the same two calls; env.stride_report() gives swing time, foot clearance
+        # against rewards.target_feet_height, step length / width, stride time against
+        # rewards.cycle_time, cadence and left / right asymmetry.  Off, the two calls launch what they did.
+        strides = False
 
     class noise:
         add_noise = True

@@ -24,6 +24,12 @@ into the ring ``depth_buffer``; off (the default) nothing of it exists.
 the pre-reset state between hg_step and hg_post (hg_metrics_sample) and folds finished episodes right
 after hg_post (hg_metrics_fold); ``gait_report()`` turns the accumulators into tracking errors, cost
 of transport, slip, support fractions and the fall rate.  Off (the default) nothing of it exists.
+
+``metrics.strides`` (BUILD-DEFINED, needs ``metrics.gait``) adds a per-foot stride detector to the
+same two calls: lift-off, apex and touchdown of every step give swing time, foot clearance, step
+length and width, touchdown force, stride length and stride time; ``stride_report()`` compares them
+with ``rewards.target_feet_height`` and ``rewards.cycle_time``.  Off (the default) nothing of it
+exists and the two calls launch what they did.
 """
 import ctypes
 
@@ -96,6 +102,77 @@ def gait_report_arrays(done, counts, total_mass, gravity, dt, terrain_types=None
     m, t = np.asarray(total_mass, np.float64).reshape(-1), np.asarray(terrain_types).reshape(-1).astype(np.int64)
     return {"overall": row,
             "terrain_types": {int(k): gait_report_row(d[:, t == k], c[:, t == k], m[t == k], gravity, dt)
+                              for k in np.unique(t)}}
+
+
+STRIDE_FEET = ("left", "right")  # cfg.feet_body order: the asset lists the left leg first
+
+
+def _stride_row(tot, episodes, feet, target_feet_height, cycle_time):
+    """The figures of one row from summed accumulator slots (a dict by _native.STRIDE_NAMES)."""
+    strides, pairs = tot["strides"], tot["stride_pairs"]
+    mean_swing = _ratio(tot["swing_time"], strides)
+    mean_clear = _ratio(tot["clearance"], strides)
+    mean_stride_time = _ratio(tot["stride_time"], pairs)
+
+    def over(v, den):
+        return None if v is None or not den > 0 else v / float(den)
+    return {
+        "strides": int(strides), "strides_per_episode": _ratio(strides, episodes),
+        "mean_swing_time": mean_swing, "mean_clearance": mean_clear,
+        "clearance_vs_target": over(mean_clear, target_feet_height),  # 1.0: the swing apex is at the target
+        "mean_step_length": _ratio(tot["step_length"], strides), "mean_step_width": _ratio(tot["step_width"], strides),
+        "mean_touchdown_force": _ratio(tot["touchdown_force"], strides),
+        "mean_stride_length": _ratio(tot["stride_length"], pairs), "mean_stride_time": mean_stride_time,
+        "stride_time_vs_cycle": over(mean_stride_time, cycle_time),  # 1.0: a stride takes rewards.cycle_time
+        # touchdowns per second: each of the row's feet lands once per stride
+        "cadence": None if mean_stride_time is None else over(float(feet), mean_stride_time),
+        "swing_fraction": None if mean_swing is None else over(mean_swing, mean_stride_time or 0.0),
+        "short_swing_fraction": _ratio(tot["short_swings"], strides + tot["short_swings"]),
+    }
+
+
+def stride_report_row(done, counts, dt, target_feet_height, cycle_time):
+    """Stride figures from accumulator arrays, on the host in float64: {"left": row, "right": row,
+    "both": row}.  done: [20, n] completed-episode stride sums (HG_T_STRIDE_DONE, foot-major, slots
+    _native.STRIDE_NAMES); counts: [4, n] episodes, falls, time_outs, skipped (HG_T_METRICS_COUNT);
+    dt: the policy step (the sums already carry it; kept for callers that want samples:
+    mean_swing_time / dt); target_feet_height, cycle_time: rewards.target_feet_height / cycle_time.
+    Means are per stride (clearance, step length and width, touchdown force, swing time) or per pair
+    of consecutive touchdowns of one foot (stride length and time); swing_fraction is mean swing time
+    over mean stride time; `both` adds the two asymmetries, (left - right) / their mean.  A figure
+    whose divisor is zero is None."""
+    ns = len(N.STRIDE_NAMES)
+    d = np.ascontiguousarray(np.asarray(done, np.float64).reshape(2 * ns, -1))
+    episodes = int(np.asarray(counts, np.int64).reshape(len(N.METRICS_COUNT_NAMES), -1)[0].sum())
+    sums = d.sum(axis=1)
+    per_foot = [dict(zip(N.STRIDE_NAMES, sums[f * ns:(f + 1) * ns])) for f in range(2)]
+    rows = {name: _stride_row(per_foot[f], episodes, 1, target_feet_height, cycle_time)
+            for f, name in enumerate(STRIDE_FEET)}
+    both = _stride_row({k: per_foot[0][k] + per_foot[1][k] for k in N.STRIDE_NAMES}, episodes, 2, target_feet_height,
+                       cycle_time)
+
+    def asym(key):
+        a, b = rows["left"][key], rows["right"][key]
+        if a is None or b is None or a + b == 0:
+            return None
+        return (a - b) / ((a + b) / 2.0)
+    both["swing_time_asymmetry"] = asym("mean_swing_time")
+    both["step_length_asymmetry"] = asym("mean_step_length")
+    rows["both"] = both
+    return rows
+
+
+def stride_report_arrays(done, counts, dt, target_feet_height, cycle_time, terrain_types=None):
+    """stride_report_row over all envs; with terrain_types ([n] ints) a dict
+    {"overall": rows, "terrain_types": {type: rows}} with one entry per value present."""
+    rows = stride_report_row(done, counts, dt, target_feet_height, cycle_time)
+    if terrain_types is None:
+        return rows
+    d, c = np.asarray(done, np.float64), np.asarray(counts, np.int64)
+    t = np.asarray(terrain_types).reshape(-1).astype(np.int64)
+    return {"overall": rows,
+            "terrain_types": {int(k): stride_report_row(d[:, t == k], c[:, t == k], dt, target_feet_height, cycle_time)
                               for k in np.unique(t)}}
 
 
@@ -209,7 +286,12 @@ def build_hg_cfg(cfg, num_envs, sim_dt, seed, model_js, heightfield=None, hf_sha
     c.cmd_curriculum = int(bool(getattr(cfg.commands, "curriculum", False)))
     c.cmd_max_curriculum = float(getattr(cfg.commands, "max_curriculum", 0.0))
     # gait metrics (BUILD-DEFINED, include/hgsim.h hg_cfg.gait_metrics)
+    # a bit field: bit 0 the per-sample metrics, bit 1 the stride detector (metrics.strides), which needs bit 0
     c.gait_metrics = int(bool(getattr(getattr(cfg, "metrics", None), "gait", False)))
+    if bool(getattr(getattr(cfg, "metrics", None), "strides", False)):
+        if not c.gait_metrics:
+            raise ValueError("metrics.strides needs metrics.gait: the stride detector runs inside the gait-metrics calls")
+        c.gait_metrics |= 2
     # per-episode actuator randomisation (BUILD-DEFINED, include/hgsim.h hg_cfg.actuator_rand)
     dr = cfg.domain_rand
     c.actuator_rand = int(bool(getattr(dr, "randomize_actuators", False)))
@@ -587,6 +669,15 @@ class XBotLFreeEnv(BaseTask):
             self.clear_gait_metrics = self._clear_gait_metrics
             self.gait_report = self._gait_report
             self.gait_pack = self._gait_pack
+        self._strides = bool(self._hgcfg.gait_metrics & 2)
+        if self._strides:
+            # metrics.strides: per-foot stride sums of the running episode and of the completed ones
+            # ([20, N] float64, row f * 10 + slot) and the detector's state ([16, N], row f * 8 + slot)
+            self.stride_running = self._view(T["STRIDE_RUN"])
+            self.stride_completed = self._view(T["STRIDE_DONE"])
+            self.stride_state = self._view(T["STRIDE_STATE"])
+            self.stride_names = list(N.STRIDE_NAMES)
+            self.stride_report = self._stride_report
 
     def _global_ids(self):
         """(offset, total): this shard's envs are global ids [offset, offset + num_envs) of total."""
@@ -828,11 +919,15 @@ class XBotLFreeEnv(BaseTask):
 
     def _gait_pack(self):
         """[19, N] float64 on the device: the completed rows, the four counters, body_mass and the
-        terrain types (0 on the plane) — everything a report needs, for one device-to-host copy."""
+        terrain types (0 on the plane) — everything a report needs, for one device-to-host copy.
+        With metrics.strides the [20, N] completed stride sums follow as rows 19..38."""
         tt = getattr(self, "terrain_types", None)
         tt = torch.zeros(1, self.num_envs, dtype=torch.float64, device=self.device) if tt is None else tt.view(1, -1)
-        return torch.cat([self.metrics_completed, self.metrics_counts.to(torch.float64),
-                          self.body_mass.view(1, -1).to(torch.float64), tt.to(torch.float64)])
+        rows = [self.metrics_completed, self.metrics_counts.to(torch.float64),
+                self.body_mass.view(1, -1).to(torch.float64), tt.to(torch.float64)]
+        if self._strides:
+            rows.append(self.stride_completed)
+        return torch.cat(rows)
 
     def gait_report_from_packed(self, packed, by_terrain_type=False):
         """The report from a host copy of gait_pack() (the runner copies it asynchronously)."""
@@ -853,12 +948,36 @@ class XBotLFreeEnv(BaseTask):
         by_terrain_type: {"overall": row, "terrain_types": {type: row}}."""
         return self.gait_report_from_packed(self._gait_pack().cpu().numpy(), by_terrain_type)
 
+    # ------------------------------------------------------------------ stride statistics
+    _strides = False  # metrics.strides
+
+    def stride_report_from_packed(self, packed, by_terrain_type=False):
+        """The stride report from a host copy of gait_pack() (rows 13..16 the counters, 18 the terrain
+        types, 19..38 the completed stride sums)."""
+        a = np.asarray(packed, np.float64)
+        rw = self.cfg.rewards
+        return stride_report_arrays(a[19:39], np.rint(a[13:17]).astype(np.int64),
+                                    float(self._hgcfg.sim_dt) * int(self._hgcfg.decimation),
+                                    float(rw.target_feet_height), float(rw.cycle_time),
+                                    np.rint(a[18]).astype(np.int64) if by_terrain_type else None)
+
+    def _stride_report(self, by_terrain_type=False):
+        """Stride figures over the episodes completed since the last clear_gait_metrics(), on the host
+        in float64 from one device-to-host copy (a host wait: nothing on the step path calls it):
+        rows `left`, `right` and `both` of stride_report_row — strides, swing time, foot clearance
+        against rewards.target_feet_height, step length and width, touchdown force, stride length,
+        stride time against rewards.cycle_time, cadence, swing fraction, chatter fraction and, in
+        `both`, the left / right asymmetries.  by_terrain_type: {"overall": rows, "terrain_types":
+        {type: rows}}."""
+        return self.stride_report_from_packed(self._gait_pack().cpu().numpy(), by_terrain_type)
+
     def _launch_reset(self, mask_u8):
         mp = ctypes.c_void_p(mask_u8.data_ptr()) if mask_u8 is not None else None
         N.check(self.hg.hg_reset_masked(self.sim, mp, ctypes.c_uint64(self.common_step_counter), self._stream()),
                 self.sim)
         if self._gait:
-            # a manual reset discards the running episode of the envs it resets: it is not counted
+            # a manual reset discards the running episode (and, with metrics.strides, the running
+            # stride sums and the detector state) of the envs it resets: it is not counted
             N.check(self.hg.hg_metrics_fold(self.sim, 1, mp, self._stream()), self.sim)
         self._publish_extras()
 

@@ -5,7 +5,7 @@ RMS errors, distance per episode, cost of transport, foot slip per metre, tilt, 
 peak torque ratio, episodes and the fall rate — overall and per terrain type.
 
     python -m humanoid.scripts.evaluate --load_model policy_1.pt [--envs 256] [--duration 20]
-        [--command VX VY WZ] [--terrain plane|heightfield|trimesh] [--seed 5] [--out DIR]
+        [--command VX VY WZ] [--terrain plane|heightfield|trimesh] [--seed 5] [--out DIR] [--strides]
 
 ``--load_model`` is read as scripts/sim2sim.py reads it (TorchScript export, ONNX actor or weights
 npz).  ``--command`` fixes every env's command for the whole run (no resampling, no heading
@@ -13,6 +13,11 @@ command); without it the env samples commands as in training.  Episodes still ru
 duration ends are not part of the report (it covers completed episodes), so the duration should
 be longer than env.episode_length_s unless falls are the point.  BUILD-DEFINED: the reference has
 no such script.
+
+``--strides`` turns metrics.strides on as well and adds a ``"strides"`` section to the report
+(env.stride_report: swing time, foot clearance against rewards.target_feet_height, step length and
+width, stride time against rewards.cycle_time, cadence, asymmetry; rows left / right / both, overall
+and per terrain type).  Without the flag the output is what it was.
 """
 import argparse
 import json
@@ -28,9 +33,15 @@ ROW_ORDER = ["episodes", "falls", "time_outs", "fall_rate", "steps", "skipped", 
              "flight_fraction", "peak_torque_ratio", "mean_torque2", "action_rate_rms"]
 
 
-def make_cfg(num_envs, duration, command=None, terrain="plane", seed=5):
-    """XBotLCfg of the training env with gait metrics on; a fixed command turns resampling and the
-    heading command off."""
+STRIDE_ROW_ORDER = ["strides", "strides_per_episode", "mean_swing_time", "mean_clearance", "clearance_vs_target",
+                    "mean_step_length", "mean_step_width", "mean_touchdown_force", "mean_stride_length",
+                    "mean_stride_time", "stride_time_vs_cycle", "cadence", "swing_fraction", "short_swing_fraction",
+                    "swing_time_asymmetry", "step_length_asymmetry"]
+
+
+def make_cfg(num_envs, duration, command=None, terrain="plane", seed=5, strides=False):
+    """XBotLCfg of the training env with gait metrics on (strides: the stride detector as well); a
+    fixed command turns resampling and the heading command off."""
     from humanoid.envs import XBotLCfg
     cfg = XBotLCfg()
     cfg.seed = int(seed)
@@ -39,6 +50,7 @@ def make_cfg(num_envs, duration, command=None, terrain="plane", seed=5):
     if terrain == "plane":
         cfg.terrain.curriculum = False
     cfg.metrics.gait = True
+    cfg.metrics.strides = bool(strides)
     if command is not None:
         if len(command) != 3:
             raise ValueError(f"--command takes VX VY WZ, got {list(command)}")
@@ -47,17 +59,21 @@ def make_cfg(num_envs, duration, command=None, terrain="plane", seed=5):
     return cfg
 
 
-def evaluate(policy, num_envs=256, duration=20.0, command=None, terrain="plane", seed=5, device="cuda:0", env=None):
+def evaluate(policy, num_envs=256, duration=20.0, command=None, terrain="plane", seed=5, device="cuda:0", env=None,
+             strides=False):
     """Run `policy` (a callable [N, num_obs] -> [N, 12]) for `duration` simulated seconds; returns
-    (report, env): env.gait_report(by_terrain_type=True) plus the run's settings."""
+    (report, env): env.gait_report(by_terrain_type=True) plus the run's settings and, with strides,
+    a "strides" section, env.stride_report(by_terrain_type=True)."""
     from humanoid.envs.custom.humanoid_env import XBotLFreeEnv
     from humanoid.utils.helpers import SimParams
     if env is None:
         torch.manual_seed(seed)
         np.random.seed(seed)
-        env = XBotLFreeEnv(make_cfg(num_envs, duration, command, terrain, seed), SimParams(), "hg_sim", device, True)
+        env = XBotLFreeEnv(make_cfg(num_envs, duration, command, terrain, seed, strides), SimParams(), "hg_sim", device, True)
     if not hasattr(env, "gait_report"):
         raise ValueError("evaluate needs an env with metrics.gait on")
+    if strides and not hasattr(env, "stride_report"):
+        raise ValueError("evaluate(strides=True) needs an env with metrics.strides on")
     cmd = None if command is None else torch.tensor([float(v) for v in command], dtype=torch.float32, device=env.device)
     steps = int(round(duration / env.dt))
     clip_a = env.cfg.normalization.clip_actions
@@ -70,6 +86,8 @@ def evaluate(policy, num_envs=256, duration=20.0, command=None, terrain="plane",
             actions = torch.clamp(policy(obs.detach()).float(), -clip_a, clip_a)
             obs, _, _, _, _ = env.step(actions)
     report = env.gait_report(by_terrain_type=True)
+    if strides:
+        report["strides"] = env.stride_report(by_terrain_type=True)
     report["settings"] = dict(envs=env.num_envs, duration_s=float(duration), steps=steps, policy_dt=float(env.dt),
                               command=None if command is None else [float(v) for v in command],
                               terrain=env.cfg.terrain.mesh_type, seed=int(seed))
@@ -94,6 +112,28 @@ def format_report(report):
     return "\n".join(lines)
 
 
+def format_stride_report(report):
+    """env.stride_report(by_terrain_type=True) as text: the left / right / both table overall, then
+    one per terrain type (none when there is a single type)."""
+    def cell(v):
+        if v is None:
+            return "-"
+        return f"{v:d}" if isinstance(v, (int, np.integer)) else f"{v:.4f}"
+
+    def table(title, rows):
+        cols = ["left", "right", "both"]
+        width = max(len(n) for n in STRIDE_ROW_ORDER)
+        lines = [f"{title:<{width}s}" + "".join(f"{c:>14s}" for c in cols)]
+        for n in STRIDE_ROW_ORDER:
+            lines.append(f"{n:<{width}s}" + "".join(f"{cell(rows[c].get(n)) if n in rows[c] else '':>14s}" for c in cols))
+        return lines
+    lines = table("overall", report["overall"])
+    if len(report["terrain_types"]) > 1:
+        for k, rows in sorted(report["terrain_types"].items()):
+            lines += table(f"type {k}", rows)
+    return "\n".join(lines)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--load_model", required=True,
@@ -105,15 +145,23 @@ def main(argv=None):
     ap.add_argument("--terrain", default="plane", choices=["plane", "heightfield", "trimesh"])
     ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--out", default=None, help="output directory (default: next to the policy)")
+    ap.add_argument("--strides", action="store_true",
+                    help="also run the stride detector (metrics.strides) and add a \"strides\" section")
     a = ap.parse_args(argv)
     policy = load_policy(a.load_model)
-    report, _ = evaluate(policy, a.envs, a.duration, a.command, a.terrain, a.seed)
+    report, _ = evaluate(policy, a.envs, a.duration, a.command, a.terrain, a.seed, strides=a.strides)
     out = a.out or os.path.join(os.path.dirname(os.path.abspath(a.load_model)), "evaluate")
     os.makedirs(out, exist_ok=True)
     path = os.path.join(out, "gait_report.json")
     with open(path, "w") as f:
-        json.dump({**report, "terrain_types": {str(k): v for k, v in report["terrain_types"].items()}}, f, indent=1)
+        doc = {**report, "terrain_types": {str(k): v for k, v in report["terrain_types"].items()}}
+        if "strides" in report:
+            st = report["strides"]
+            doc["strides"] = {**st, "terrain_types": {str(k): v for k, v in st["terrain_types"].items()}}
+        json.dump(doc, f, indent=1)
     print(format_report(report))
+    if "strides" in report:
+        print(format_stride_report(report["strides"]))
     print(f"{report['settings']['envs']} envs x {report['settings']['duration_s']:.1f} s -> {path}")
     return report
 

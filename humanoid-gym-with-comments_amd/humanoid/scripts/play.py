@@ -16,7 +16,8 @@ as ``DIR/frame_%05d.png``; when ``cv2`` is importable the frames also go into ``
 filmed.  There is no interactive viewer.
 
 With ``metrics.gait`` on in the task's config play ends by printing env.gait_report (tracking errors,
-cost of transport, slip, fall rate, ...) over the episodes the rollout completed.
+cost of transport, slip, fall rate, ...) over the episodes the rollout completed; with
+``metrics.strides`` as well, env.stride_report (clearance, step length, stride time, cadence, ...).
 
 Reference defect fixed: play.py:77 sets ``train_cfg.runner.resume = True``, but
 ``make_alg_runner`` resets it to False before reading it (task_registry.py:137), so without an
@@ -132,6 +133,10 @@ def play(args, steps=100, record=None, record_env=0, record_every=1):
         from humanoid.scripts.evaluate import format_report
         print("Gait metrics over the completed episodes:")
         print(format_report(env.gait_report(by_terrain_type=True)))
+    if hasattr(env, "stride_report"):  # metrics.strides: the completed episodes' stride figures
+        from humanoid.scripts.evaluate import format_stride_report
+        print("Stride statistics over the completed episodes:")
+        print(format_stride_report(env.stride_report(by_terrain_type=True)))
     return np.array(actions_log)
 
 

@@ -182,10 +182,13 @@ typedef struct hg_cfg {
   float critic_height_scale;            /* normalization.obs_scales.height_measurements */
   /* gait metrics (BUILD-DEFINED: the reference only has Logger.log_rewards; 0 = off, and then nothing
    * changes: no buffer is laid out, nothing is launched, and the three hg_metrics_* entry points
-   * return HG_ERR_ARG).  != 0: hg_create lays out HG_T_METRICS_RUN / _DONE / _COUNT and the caller
-   * brackets every hg_post with hg_metrics_sample and hg_metrics_fold (below).  The field lays out the
-   * arena: hg_update_cfg refuses a change.  (It fills the four bytes of padding in front of the
-   * pointer below, so no other field moves and sizeof(hg_cfg) stays.) */
+   * return HG_ERR_ARG).  A bit field.  Bit 0 (value 1): hg_create lays out HG_T_METRICS_RUN / _DONE /
+   * _COUNT and the caller brackets every hg_post with hg_metrics_sample and hg_metrics_fold (below).
+   * Bit 1 (value 3 with bit 0): the stride detector as well: hg_create also lays out HG_T_STRIDE_RUN /
+   * _DONE / _STATE and the same three entry points also run the stride launches (stride statistics,
+   * below).  hg_create refuses 2 alone (strides need the metrics) and any other value.  The field
+   * lays out the arena: hg_update_cfg refuses any change of its value.  (It fills the four bytes of
+   * padding in front of the pointer below, so no other field moves and sizeof(hg_cfg) stays.) */
   int32_t gait_metrics;
   const float* critic_height_points;    /* device f32 [P, 2] base-frame sample grid, caller-owned (the
                                          * _init_height_points grid, :314-328, x-major) */
@@ -250,6 +253,11 @@ enum hg_tensor_id {
   HG_T_METRICS_RUN,      /* [13,N] f64, SoA strides (np,1): the running episode's slot sums (hg_metrics_sample) */
   HG_T_METRICS_DONE,     /* [13,N] f64: the slot sums over the env's completed episodes (hg_metrics_fold) */
   HG_T_METRICS_COUNT,    /* [4,N] int32: completed episodes, falls, time_outs, skipped samples */
+  /* the stride detector's buffers (hg_cfg.gait_metrics bit 1; without it they have no storage and
+   * hg_tensor refuses them), foot-major: row f * slots + k is slot k of foot cfg.feet_body[f] */
+  HG_T_STRIDE_RUN,       /* [20,N] f64, SoA strides (np,1): the running episode's stride sums, 10 slots per foot */
+  HG_T_STRIDE_DONE,      /* [20,N] f64: the stride sums over the env's completed episodes */
+  HG_T_STRIDE_STATE,     /* [16,N] f64: each foot's detector state, 8 slots per foot */
   HG_T_ENV_ROWS,         /* [N] int32, read-only diagnostic: constraint rows of each env in the latest hg_step (the
                             wave-balancing sort key) */
   HG_T_ENV_ORDER,        /* [N] int32, read-only diagnostic: the env K_step's half-wave k runs, as the latest post
@@ -396,6 +404,69 @@ int hg_measure_heights(void* sim, const float* points_xy, int num_points, float*
 int hg_metrics_sample(void* sim, void* stream);
 int hg_metrics_fold(void* sim, int mode, const uint8_t* mask, void* stream);
 int hg_metrics_clear(void* sim, void* stream);
+
+/* ---- stride statistics (BUILD-DEFINED; hg_cfg.gait_metrics bit 1) ----
+ * The metrics above are sums taken sample by sample; a step is an event that spans samples:
+ * lift-off, apex, touchdown.  With bit 1 set the three entry points above also run a per-env,
+ * per-foot stride detector (k_stride_sample after k_metrics_sample, k_stride_fold after
+ * k_metrics_fold; one thread per env owns both feet, float64, no atomics, capturable); with it clear
+ * they launch exactly what they did.  csrc/hg_stride_sample.h is the statement.
+ * Inputs of one sample of env e, taken where hg_metrics_sample takes its sample (after hg_step,
+ * before hg_post: the physical, pre-reset state), every f32 converted to double, all arithmetic
+ * double in the written order, without fused multiply-add:
+ *   for the feet f = cfg.feet_body[0..1]: fz = the world HG_T_CONTACT_FORCES z, p = the body position
+ *   x, y, z (fields 0..2 of HG_T_RIGID_STATE);  q = the root quaternion times 1 / its norm;
+ *   dt = (double)sim_dt * decimation;  a foot is in contact when fz > 5 (strict, as above).
+ *   Height above ground:  hag = p.z - h(p.x, p.y);  h = 0 on a plane, otherwise
+ *   vertical_scale * min(hf[i][j], hf[i+1][j], hf[i][j+1]) with (i, j) = (p + border) /
+ *   horizontal_scale, truncated, clipped to [0, rows-2] x [0, cols-2] (hg_measure_heights'
+ *   quantisation on the world x, y itself, no yaw rotation).  This is the measured-heights rule, not
+ *   the triangulated surface the contacts see: deliberately, so the figure matches what the critic's
+ *   height samples report; next to a riser the foot reads the lower tread.
+ *   Heading:  fx = 1 - 2 (qy^2 + qz^2), fy = 2 (qx qy + qz qw), n = sqrt(fx^2 + fy^2); if n is not > 0
+ *   the sample counts as non-finite; otherwise hx = fx / n, hy = fy / n.
+ *   The landing foot relative to the other foot, r = p_f.xy - p_other.xy:
+ *   along = r . (hx, hy),  lat = r.y hx - r.x hy.
+ * State per foot, HG_T_STRIDE_STATE row f * 8 + k:
+ *     state 0  phase        0 none, 1 stance, 2 swing, 3 swing whose lift-off was not seen
+ *     state 1  phase_steps  samples in the current phase
+ *     state 2  since_td     samples since the anchoring touchdown
+ *     state 3  has_anchor   1 once a touchdown has set the anchor
+ *     state 4  anchor_x     world x, y of the foot at that touchdown
+ *     state 5  anchor_y
+ *     state 6  ref_hag      hag of the latest stance sample
+ *     state 7  apex_hag     the largest hag of the swing in progress
+ * Accumulators per foot, HG_T_STRIDE_RUN / _DONE row f * 10 + k:
+ *     stride 0  strides          valid swings that ended in a touchdown
+ *     stride 1  swing_time       += phase_steps * dt
+ *     stride 2  clearance        += apex_hag - ref_hag   (negative when the foot only descends, e.g.
+ *                                   stepping down: the last stance height is the higher one)
+ *     stride 3  step_length      += along
+ *     stride 4  step_width       += |lat|
+ *     stride 5  touchdown_force  += fz of the touchdown sample
+ *     stride 6  stride_pairs     touchdowns that had an anchor (two consecutive touchdowns of one foot)
+ *     stride 7  stride_length    += sqrt(dx^2 + dy^2) from the anchor
+ *     stride 8  stride_time      += since_td * dt
+ *     stride 9  short_swings     swings of fewer than HG_STRIDE_MIN_SWING = 3 samples (contact chatter)
+ * Per sample both feet's inputs are read first, then foot 0 is advanced, then foot 1:
+ *   any input read non-finite: nothing is added and both feet's state rows are zeroed, so no stride
+ *     spans the gap (a non-finite value in an element the sample does not read has no effect);
+ *   phase 0: phase = contact ? 1 : 3, phase_steps = 1; in contact ref_hag = hag, else apex_hag = hag;
+ *   phase 1, in contact: phase_steps += 1, ref_hag = hag, since_td += has_anchor;
+ *   phase 1, not in contact (lift-off): phase = 2, phase_steps = 1, apex_hag = hag, ref_hag is kept,
+ *     since_td += has_anchor;
+ *   phase 2 or 3, not in contact: phase_steps += 1, apex_hag = max(apex_hag, hag), since_td += has_anchor;
+ *   phase 2, in contact (touchdown): since_td += has_anchor, then
+ *     phase_steps < 3: short_swings += 1, the anchor and since_td are left alone;
+ *     otherwise: slots 0-5 as above; with has_anchor also slots 6-8; then anchor = p.xy,
+ *       has_anchor = 1, since_td = 0;
+ *     either way phase = 1, phase_steps = 1, ref_hag = hag;
+ *   phase 3, in contact: anchor = p.xy, has_anchor = 1, since_td = 0, phase = 1, phase_steps = 1,
+ *     ref_hag = hag; no stride is counted.
+ * hg_metrics_fold, mode 0: for every env with HG_T_RESET_BUF[e] set, HG_T_STRIDE_RUN is added to
+ *   HG_T_STRIDE_DONE, RUN and STATE are zeroed (a swing in progress is discarded); other envs are
+ *   untouched.  mode 1: the masked envs' (NULL = all) RUN and STATE are zeroed, nothing is added.
+ * hg_metrics_clear zeroes the three stride buffers too.  Columns e >= N are never written. */
 
 /* ---- base-mounted depth camera (replaces the camera sensor attach_camera creates,
  * humanoid_env.py:399-423, and its depth image; BUILD-DEFINED: there is no graphics pipeline here,
