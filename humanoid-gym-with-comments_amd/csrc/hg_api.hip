@@ -21,6 +21,9 @@ extern "C" int hg_launch_actuator_draw(const HgState* S, uint64_t counter, int m
                                        hipStream_t stream);
 extern "C" int hg_launch_depth(const HgState* S, const hg_cfg* hcfg, const hg_depth_cam* cam, const float* pitch,
                                float* out, int64_t env_stride, uint64_t counter, int mapping, hipStream_t stream);
+extern "C" int hg_launch_depth_robot(const HgState* S, const hg_cfg* hcfg, const hg_model* model, const hg_depth_cam* cam,
+                                     const float* pitch, float* table, float* out, int64_t env_stride, uint64_t counter,
+                                     hipStream_t stream);
 extern "C" int hg_launch_view_pose(const HgState* S, const hg_model* model, const int32_t* env_ids, int n, float* out,
                                    int* num_shapes, hipStream_t stream);
 extern "C" int hg_launch_view(const HgState* S, const hg_cfg* hcfg, const hg_view_cam* cam, const double* fwd,
@@ -147,7 +150,7 @@ Layout make_layout(const hg_cfg* c) {
   L.noise_counter = o; o += align256(sizeof(uint64_t));
   L.env_rows = o; o += align256((size_t)np * 4);
   L.env_order = o; o += align256((size_t)np * 4);
-  L.view_table = o; o += align256((size_t)n * 16 * 16 * 4);  // hg_render_view's world shape table, a row per selected env
+  L.view_table = o; o += align256((size_t)n * 16 * 16 * 4);  // hg_render_view's world shape table, a row per selected env; hg_render_depth_robot's rows of every env
   L.off[HG_T_OBS_BUF] = L.obs_buf;
   L.off[HG_T_PRIV_BUF] = L.priv_buf;
   L.off[HG_T_ENV_ROWS] = L.env_rows;
@@ -682,6 +685,28 @@ extern "C" int hg_render_depth(void* sim, const hg_depth_cam* cam, const float* 
   const int mapping = (m && strcmp(m, "rows") == 0) ? 1 : 0;
   if (hg_launch_depth(&s->S, &s->cfg, cam, pitch, out, env_stride, counter, mapping, (hipStream_t)stream) != 0)
     return fail(s, HG_ERR_HIP, "k_depth launch failed");
+  return HG_OK;
+}
+
+// the same camera with the robot's own legs drawn (hg_depth_robot.hip); the argument checks of hg_render_depth
+extern "C" int hg_render_depth_robot(void* sim, const hg_depth_cam* cam, const float* pitch, float* out,
+                                     int64_t env_stride, uint64_t counter, void* stream) {
+  Sim* s = (Sim*)sim;
+  if (!s || !cam || !out) return fail(s, HG_ERR_ARG, "hg_render_depth_robot: null argument");
+  if (cam->width <= 0 || cam->height <= 0)
+    return fail(s, HG_ERR_ARG, "hg_render_depth_robot: width and height must be > 0");
+  if ((int64_t)cam->width * cam->height > 262144)
+    return fail(s, HG_ERR_ARG, "hg_render_depth_robot: more than 262144 pixels (the noise draw's 16-bit block index)");
+  if (env_stride < (int64_t)cam->width * cam->height)
+    return fail(s, HG_ERR_ARG, "hg_render_depth_robot: env_stride below width * height");
+  if (!(cam->near_clip >= 0.f) || !(cam->far_clip > cam->near_clip) || !(cam->far_clip < INFINITY))
+    return fail(s, HG_ERR_ARG, "hg_render_depth_robot: need 0 <= near_clip < far_clip < inf");
+  if (!(cam->horizontal_fov_deg > 0.f) || !(cam->horizontal_fov_deg < 180.f))
+    return fail(s, HG_ERR_ARG, "hg_render_depth_robot: horizontal_fov_deg must be inside (0, 180)");
+  if (!(cam->noise >= 0.f)) return fail(s, HG_ERR_ARG, "hg_render_depth_robot: noise must be >= 0");
+  float* table = (float*)(s->arena + s->L.view_table);  // shared with hg_render_view, in stream order
+  if (hg_launch_depth_robot(&s->S, &s->cfg, &s->model, cam, pitch, table, out, env_stride, counter, (hipStream_t)stream) != 0)
+    return fail(s, HG_ERR_HIP, "k_depth_pose / k_depth_robot launch failed");
   return HG_OK;
 }
 

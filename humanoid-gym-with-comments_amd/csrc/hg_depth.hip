@@ -158,7 +158,54 @@ __host__ __device__ inline float depth_march(bool field, const int16_t* __restri
   return t;
 }
 
-#ifndef HG_DEPTH_MARCH_ONLY  // hg_view.hip includes this file for depth_march alone
+// The launch parameters of a camera; shared with hg_depth_robot.hip.  The arguments were checked.
+inline DepthParams depth_params(const hg_cfg* hcfg, const hg_depth_cam* cam, int64_t env_stride, uint64_t counter) {
+  DepthParams P;
+  P.W = cam->width;
+  P.H = cam->height;
+  const double half_fov = 0.5 * (double)cam->horizontal_fov_deg * (M_PI / 180.0);
+  const double tan_h = tan(half_fov);
+  P.inv_fx = (float)(tan_h / (0.5 * P.W));
+  P.half_w = 0.5f * P.W;
+  P.half_h = 0.5f * P.H;
+  for (int i = 0; i < 3; i++) P.pos[i] = cam->pos[i];
+  P.near_clip = cam->near_clip;
+  P.far_clip = cam->far_clip;
+  P.normalize = cam->normalize != 0;
+  P.noise = cam->noise;
+  // trip bound: a ray of planar depth far is far |d| long, |d| <= dmax at the image corner, and a
+  // segment of L cells' length crosses at most sqrt(2) L + 2 cells; never more than the field has
+  // rows + columns (the march stays inside the extent)
+  P.max_steps = 1;
+  if (hcfg->terrain_type != 0 && hcfg->heightfield != nullptr) {
+    const double dmax = sqrt(1.0 + tan_h * tan_h * (1.0 + ((double)P.H / P.W) * ((double)P.H / P.W)));
+    const double geo = ceil((double)cam->far_clip * dmax / (double)hcfg->hf_horizontal_scale * 1.4142135623730951) + 4.0;
+    const double ext = (double)hcfg->hf_rows + (double)hcfg->hf_cols + 4.0;
+    P.max_steps = (int)(geo < ext ? geo : ext);  // geo is NaN-free: the arguments are finite
+    if (P.max_steps < 1) P.max_steps = 1;
+  }
+  P.tiles_x = (P.W + 7) / 8;
+  P.tiles = P.tiles_x * ((P.H + 7) / 8);
+  P.env_stride = env_stride;
+  P.counter = counter;
+  return P;
+}
+
+// The pixel's value from its planar depth t: noise, clamp, normalisation (include/hgsim.h).
+__device__ __forceinline__ float depth_pixel_value(const hg_cfg* cfg, const DepthParams& P, int e, int pix, float t) {
+  float d = t;
+  if (P.noise > 0.f) {
+    const u4 w = rng4(cfg, (uint32_t)e, P.counter, (uint32_t)pix >> 2, RNG_DEPTH_NOISE);
+    const int k = pix & 3;
+    const uint32_t word = k == 0 ? w.x : (k == 1 ? w.y : (k == 2 ? w.z : w.w));
+    d += P.noise * (2.0f * u01(word) - 1.0f);
+  }
+  d = fminf(fmaxf(d, P.near_clip), P.far_clip);
+  if (P.normalize) d = (d - P.near_clip) / (P.far_clip - P.near_clip) - 0.5f;
+  return d;
+}
+
+#ifndef HG_DEPTH_MARCH_ONLY  // hg_view.hip and hg_depth_robot.hip include this file for the march and the helpers alone
 // TILE: a wave is an 8 x 8 pixel tile (its 64 rays walk the same few cells); else 64 consecutive
 // pixels of the row-major image.
 template <bool TILE>
@@ -202,16 +249,7 @@ __global__ __launch_bounds__(DEPTH_T, 8) void k_depth(HgState S, DepthParams P, 
     const float oz = pz + off.z;
     const float t = depth_march(field, hf, rows, C, hs, vs, border, px, py, off.x, off.y, oz, D.x, D.y, D.z, zfar,
                                 P.max_steps);
-    float d = t;
-    if (P.noise > 0.f) {
-      const u4 w = rng4(cfg, (uint32_t)e, P.counter, (uint32_t)pix >> 2, RNG_DEPTH_NOISE);
-      const int k = pix & 3;
-      const uint32_t word = k == 0 ? w.x : (k == 1 ? w.y : (k == 2 ? w.z : w.w));
-      d += P.noise * (2.0f * u01(word) - 1.0f);
-    }
-    d = fminf(fmaxf(d, P.near_clip), zfar);
-    if (P.normalize) d = (d - P.near_clip) / (zfar - P.near_clip) - 0.5f;
-    out[(size_t)e * P.env_stride + pix] = d;
+    out[(size_t)e * P.env_stride + pix] = depth_pixel_value(cfg, P, e, pix, t);
   }
 }
 
@@ -224,34 +262,7 @@ __global__ __launch_bounds__(DEPTH_T, 8) void k_depth(HgState S, DepthParams P, 
 // arguments were checked by hg_render_depth.
 extern "C" int hg_launch_depth(const HgState* S, const hg_cfg* hcfg, const hg_depth_cam* cam, const float* pitch,
                                float* out, int64_t env_stride, uint64_t counter, int mapping, hipStream_t stream) {
-  DepthParams P;
-  P.W = cam->width;
-  P.H = cam->height;
-  const double half_fov = 0.5 * (double)cam->horizontal_fov_deg * (M_PI / 180.0);
-  const double tan_h = tan(half_fov);
-  P.inv_fx = (float)(tan_h / (0.5 * P.W));
-  P.half_w = 0.5f * P.W;
-  P.half_h = 0.5f * P.H;
-  for (int i = 0; i < 3; i++) P.pos[i] = cam->pos[i];
-  P.near_clip = cam->near_clip;
-  P.far_clip = cam->far_clip;
-  P.normalize = cam->normalize != 0;
-  P.noise = cam->noise;
-  // trip bound: a ray of planar depth far is far |d| long, |d| <= dmax at the image corner, and a
-  // segment of L cells' length crosses at most sqrt(2) L + 2 cells; never more than the field has
-  // rows + columns (the march stays inside the extent)
-  P.max_steps = 1;
-  if (hcfg->terrain_type != 0 && hcfg->heightfield != nullptr) {
-    const double dmax = sqrt(1.0 + tan_h * tan_h * (1.0 + ((double)P.H / P.W) * ((double)P.H / P.W)));
-    const double geo = ceil((double)cam->far_clip * dmax / (double)hcfg->hf_horizontal_scale * 1.4142135623730951) + 4.0;
-    const double ext = (double)hcfg->hf_rows + (double)hcfg->hf_cols + 4.0;
-    P.max_steps = (int)(geo < ext ? geo : ext);  // geo is NaN-free: the arguments are finite
-    if (P.max_steps < 1) P.max_steps = 1;
-  }
-  P.tiles_x = (P.W + 7) / 8;
-  P.tiles = P.tiles_x * ((P.H + 7) / 8);
-  P.env_stride = env_stride;
-  P.counter = counter;
+  const DepthParams P = depth_params(hcfg, cam, env_stride, counter);
   const unsigned gy = (unsigned)(S->n < 65535 ? S->n : 65535);
   if (mapping == 0) {
     const unsigned gx = (unsigned)((P.tiles + DEPTH_T / 64 - 1) / (DEPTH_T / 64));

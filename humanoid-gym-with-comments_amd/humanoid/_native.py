@@ -129,6 +129,16 @@ def depth_cam(depth_cfg, normalize=None, noise=None, env_stride=None):
     return cam
 
 
+def depth_draw_robot(depth_cfg):
+    """Whether a config's ``depth`` class asks for the robot's own legs in the depth image
+    (hg_render_depth_robot instead of hg_render_depth).  Raises ValueError when ``draw_robot`` is on
+    without ``use_camera``: there is no image to draw into."""
+    on = bool(getattr(depth_cfg, "draw_robot", False))
+    if on and not getattr(depth_cfg, "use_camera", False):
+        raise ValueError("depth.draw_robot needs depth.use_camera")
+    return on
+
+
 class HgViewCam(ctypes.Structure):
     """hg_view_cam (include/hgsim.h): the world or follow camera hg_render_view renders."""
     _fields_ = [("width", i32), ("height", i32), ("horizontal_fov_deg", f32), ("mode", i32), ("eye", f32 * 3),
@@ -208,7 +218,7 @@ EXPORTS = ["hg_arena_bytes", "hg_create", "hg_destroy", "hg_last_error", "hg_ten
            "hg_post", "hg_set_rollout_sink", "hg_ep_stats_slot", "hg_obs_head", "hg_obs_window_advance", "hg_update_cfg", "hg_reset_masked",
            "hg_set_command_range_x", "hg_publish_terrain_level", "hg_set_dof_state_indexed", "hg_set_root_state_indexed",
            "hg_set_root_state", "hg_set_env_props", "hg_set_actuator_props",
-           "hg_measure_heights", "hg_metrics_sample", "hg_metrics_fold", "hg_metrics_clear", "hg_render_depth", "hg_view_shapes", "hg_render_view", "hg_gae_scan", "hg_gae_stats_len", "hg_gae_normalize", "hg_adam_step", "hg_adam_chunk", "hg_kl_mean", "hg_kl_lr_rule",
+           "hg_measure_heights", "hg_metrics_sample", "hg_metrics_fold", "hg_metrics_clear", "hg_render_depth", "hg_render_depth_robot", "hg_view_shapes", "hg_render_view", "hg_gae_scan", "hg_gae_stats_len", "hg_gae_normalize", "hg_adam_step", "hg_adam_chunk", "hg_kl_mean", "hg_kl_lr_rule",
            "hg_rollout_act", "hg_rollout_act_head", "hg_rollout_act_tail", "hg_rollout_act_tail2", "hg_rollout_env", "hg_gather_rows", "hg_gather_rows_ex", "hg_gather_stacked", "hg_ppo_loss", "hg_ppo_loss_lr", "hg_ppo_loss_scratch", "hg_ppo_loss_backward",
            "hg_mirror_rows", "hg_sym_loss", "hg_sym_loss_scratch", "hg_sym_loss_backward",
            "hg_mlp_act_backward", "hg_mlp_act_backward_scratch", "hg_colsum_jobs", "hg_linear_skinny_supported",
@@ -232,14 +242,15 @@ class GatherTable(ctypes.Structure):
 
 def source_hash(pkg_root=PKG_ROOT):
     """sha256 (first 16 hex digits) of the library's sources in the Makefile's stamp order (SRCS,
-    csrc/hg_common.h, csrc/hg_view_shapes.h, csrc/hg_metrics_sample.h, csrc/hg_stride_sample.h, include/hgsim.h), as the Makefile computes it; None when the sources are
+    csrc/hg_common.h, csrc/hg_view_shapes.h, csrc/hg_view_pose.h, csrc/hg_depth_robot.h, csrc/hg_metrics_sample.h, csrc/hg_stride_sample.h, include/hgsim.h), as the Makefile computes it; None when the sources are
     not in the tree."""
     import hashlib
     try:
         with open(os.path.join(pkg_root, "Makefile")) as f:
             srcs = next(ln.split("=", 1)[1].split() for ln in f if ln.startswith("SRCS ="))
         h = hashlib.sha256()
-        for rel in srcs + ["csrc/hg_common.h", "csrc/hg_view_shapes.h", "csrc/hg_metrics_sample.h", "csrc/hg_stride_sample.h",
+        for rel in srcs + ["csrc/hg_common.h", "csrc/hg_view_shapes.h", "csrc/hg_view_pose.h", "csrc/hg_depth_robot.h",
+                           "csrc/hg_metrics_sample.h", "csrc/hg_stride_sample.h",
                            "../include/hgsim.h"]:
             with open(os.path.join(pkg_root, rel), "rb") as f:
                 h.update(f.read())
@@ -305,6 +316,8 @@ def load_library(path=LIB_PATH):
     L.hg_metrics_clear.argtypes = [vp, vp]
     L.hg_render_depth.restype = ctypes.c_int
     L.hg_render_depth.argtypes = [vp, ctypes.POINTER(HgDepthCam), vp, vp, ctypes.c_int64, ctypes.c_uint64, vp]
+    L.hg_render_depth_robot.restype = ctypes.c_int
+    L.hg_render_depth_robot.argtypes = L.hg_render_depth.argtypes
     L.hg_view_shapes.restype = ctypes.c_int
     L.hg_view_shapes.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_int32), vp]
     L.hg_render_view.restype = ctypes.c_int

@@ -99,8 +99,12 @@ class XBotLCfg(BaseConfig):
         # base-mounted forward depth camera (attach_camera, humanoid_env.py:399-423 of the
         # reference reads use_camera, original, horizontal_fov, position, angle; it ships no
         # values, so all of these are BUILD-DEFINED).  Rendered by hg_render_depth: rays marched
-        # against the terrain K_step collides with; the robot's own links are not drawn.
+        # against the terrain K_step collides with.
         use_camera = False
+        # BUILD-DEFINED: draw the robot's own legs (the six leg capsules and the two foot boxes of
+        # the hg_render_view shape table) into every frame, by hg_render_depth_robot; links of the
+        # camera's own body (base box, hands) are not drawn.  Off, no link is drawn.  Needs use_camera.
+        draw_robot = False
         original = (106, 60)              # (W, H) pixels
         horizontal_fov = 87               # degrees
         position = [0.10, 0.0, 0.15]      # in the base frame

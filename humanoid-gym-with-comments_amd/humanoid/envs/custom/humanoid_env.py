@@ -458,9 +458,11 @@ class XBotLFreeEnv(BaseTask):
     def _init_depth_camera(self):
         """attach_camera (humanoid_env.py:399-423): a forward depth camera on the base, its pitch
         drawn per env from depth.angle.  The image is ray-marched against the terrain by
-        hg_render_depth (no graphics pipeline); the robot's own links are not drawn.  Nothing is
-        created unless depth.use_camera is on."""
+        hg_render_depth (no graphics pipeline); with depth.draw_robot, hg_render_depth_robot also
+        draws the robot's legs and feet (links of the camera's own body are never drawn).  Nothing
+        is created unless depth.use_camera is on."""
         d = getattr(self.cfg, "depth", None)
+        self._depth_draw_robot = N.depth_draw_robot(d)  # refuses draw_robot without use_camera
         if d is None or not getattr(d, "use_camera", False):
             return
         self._depth = d
@@ -482,13 +484,15 @@ class XBotLFreeEnv(BaseTask):
         self.depth_frame = self._depth_frame
         self.render_depth = self._render_depth
 
-    def _launch_depth(self, cam, out, env_stride, counter):
+    def _launch_depth(self, cam, out, env_stride, counter, draw_robot=None):
+        """hg_render_depth, or hg_render_depth_robot when the robot's legs are drawn (None: depth.draw_robot)."""
         p = self.depth_cam_pitch
         if p.dtype != torch.float32 or p.shape != (self.num_envs,) or not p.is_contiguous() or p.device != self.device:
             raise ValueError(f"depth_cam_pitch must stay a contiguous float32 [{self.num_envs}] tensor on {self.device}")
-        N.check(self.hg.hg_render_depth(self.sim, ctypes.byref(cam), ctypes.c_void_p(p.data_ptr()),
-                                        ctypes.c_void_p(out.data_ptr()), ctypes.c_int64(env_stride),
-                                        ctypes.c_uint64(counter), self._stream()), self.sim)
+        robot = self._depth_draw_robot if draw_robot is None else bool(draw_robot)
+        entry = self.hg.hg_render_depth_robot if robot else self.hg.hg_render_depth
+        N.check(entry(self.sim, ctypes.byref(cam), ctypes.c_void_p(p.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                      ctypes.c_int64(env_stride), ctypes.c_uint64(counter), self._stream()), self.sim)
 
     def _render_depth_slot(self):
         """One render into the ring's next slot (noise keyed by the step counter)."""
@@ -504,10 +508,11 @@ class XBotLFreeEnv(BaseTask):
             raise ValueError(f"depth_frame: age must be in [0, {self._depth_len}), got {age}")
         return self.depth_buffer[:, (self._depth_renders - 1 - age) % self._depth_len]
 
-    def _render_depth(self, out=None, normalize=None, noise=None):
-        """Render the camera now, at the current root states, into a fresh or given contiguous
-        float32 [N, H, W] tensor (the ring is not touched).  normalize / noise override
-        depth.normalize / depth.dis_noise; the noise is keyed by the step counter."""
+    def _render_depth(self, out=None, normalize=None, noise=None, draw_robot=None):
+        """Render the camera now, at the current root states and joint positions, into a fresh or
+        given contiguous float32 [N, H, W] tensor (the ring is not touched).  normalize / noise /
+        draw_robot override depth.normalize / depth.dis_noise / depth.draw_robot; the noise is
+        keyed by the step counter."""
         cam = self._depth_cam if normalize is None and noise is None else N.depth_cam(self._depth, normalize, noise)
         h, w = cam.height, cam.width
         if out is None:
@@ -516,7 +521,7 @@ class XBotLFreeEnv(BaseTask):
               or out.device != self.device):
             raise ValueError(f"render_depth: out must be a contiguous float32 [{self.num_envs}, {h}, {w}] tensor on "
                              f"{self.device}")
-        self._launch_depth(cam, out, h * w, self.common_step_counter)
+        self._launch_depth(cam, out, h * w, self.common_step_counter, draw_robot)
         return out
 
     # ------------------------------------------------------------------ follow-camera view

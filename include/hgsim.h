@@ -490,9 +490,9 @@ int hg_metrics_clear(void* sim, void* stream);
  * Cells outside [0, rows-2] x [0, cols-2] hold no surface (a ray may enter the extent from
  * outside).  The surface is two-sided: the result is the first intersection with t >= 0 from either
  * side, so a camera under the terrain sees it from below.  No intersection within far_clip, or a
- * non-finite pose / pitch, gives far_clip.  Deviations from a rendered image: the robot's own links
- * are not drawn, and there are no vertical walls where the reference's trimesh conversion
- * (slope_treshold) would insert them.
+ * non-finite pose / pitch, gives far_clip.  Deviations from a rendered image: hg_render_depth draws
+ * no link of the robot and hg_render_depth_robot (below) none of the camera's own body; and there
+ * are no vertical walls where the reference's trimesh conversion (slope_treshold) would insert them.
  * Pixel value: raw = t; + noise * (2 u01(word) - 1) when noise > 0, the Philox draw keyed like
  * every other (seed; global env id, counter, block = pix >> 2, purpose 11), word pix & 3, pix =
  * r W + c; clamped to [near_clip, far_clip]; normalize != 0 then maps it to
@@ -511,6 +511,27 @@ typedef struct hg_depth_cam {
 } hg_depth_cam;
 int hg_render_depth(void* sim, const hg_depth_cam* cam, const float* pitch, float* out, int64_t env_stride,
                     uint64_t counter, void* stream);
+/* The same camera, image, arguments, refusals (hg_last_error starts with hg_render_depth_robot) and
+ * pixel value, with the robot's own legs in view: raw = the nearest of the terrain's t and the t of
+ * the DRAWN SHAPES, the rows of the hg_render_view shape table (csrc/hg_view_shapes.h) whose body is
+ * not body 0 — for XBot-L the six leg capsules and the two foot boxes.  Deviation from a rendered
+ * image: links of the camera's own body are not drawn.  The camera is rigidly fixed to body 0, the
+ * base box is a coarse collision bound that contains the default camera position (drawing it would
+ * put t = 0 in every pixel) and the hand capsules hang from the same body; torso, arms and head
+ * have no shapes at all.
+ * Ray rules of the drawn shapes (csrc/hg_view_shapes.h): t = 0 for a camera origin inside a shape;
+ * a hit exactly at far_clip counts; a shape ties the terrain in the shape's favour; non-finite input
+ * is a miss, so a non-finite pose still writes far_clip.  Noise, clamp and normalisation act on the
+ * combined t, with hg_render_depth's Philox key.
+ * The pose is forward kinematics of root_states and dof_pos, NOT HG_T_RIGID_STATE (see
+ * hg_render_view: an env that was just reset is drawn where it now is).  Two launches for all N
+ * envs (csrc/hg_depth_robot.hip): a pose pass that writes camera-relative rows and their pixel
+ * rectangles into the table region of the arena hg_render_view uses (stream order keeps the two
+ * apart), and hg_render_depth's pixel kernel with a per-tile shape loop.  Standalone, allocates
+ * nothing, does not synchronise (capturable).  The pixel-to-lane mapping is always 8 x 8 tiles
+ * (HG_DEPTH_MAP is not read). */
+int hg_render_depth_robot(void* sim, const hg_depth_cam* cam, const float* pitch, float* out, int64_t env_stride,
+                          uint64_t counter, void* stream);
 
 /* ---- follow-camera view of robot and terrain (replaces the camera sensor play.py attaches and its
  * IMAGE_COLOR read, scripts/play.py:84-141; BUILD-DEFINED: ray casting by a HIP kernel, no graphics
