@@ -392,9 +392,11 @@ int launch(int mode, GemmArgs g, bool vec, bool elu, hipStream_t s) {
 // ---------------------------------------------------------------------------------------------
 // f32 GEMM on the bf16 matrix cores (16x the f32 MFMA rate): every f32 operand is split exactly
 // into three bf16 terms x = x0 + x1 + x2 (x0 = bf16(x), x1 = bf16(x - x0), x2 = bf16(x - x0 - x1):
-// 24 significand bits; the rounding of x2 leaves ~2^-24 |x|, f32's own representation error), and
-// the product keeps the six terms of total order <= 2, a0 b0 + a0 b1 + a1 b0 + a0 b2 + a1 b1 +
-// a2 b0 (the dropped a1 b2 + a2 b1 + a2 b2 are ~2^-24 |a b|), each bf16 x bf16 product exact in the
+// 24 significand bits: x - x0 - x1 has at most 7 of them left, so x2 is exact and the three planes
+// sum to x), and the product keeps the six terms of total order <= 2, a0 b0 + a0 b1 + a1 b0 +
+// a0 b2 + a1 b1 + a2 b0 (the dropped a1 b2 + a2 b1 + a2 b2 are ~2^-26 |a b|: |x1| <= 2^-9 |x|,
+// |x2| <= 2^-18 |x| up to the position of x in its binade; per product |y - a b| <= 2^-21 |a b|,
+// tests/test_gpu_gemm_terms.py), each bf16 x bf16 product exact in the
 // f32 accumulator of v_mfma_f32_32x32x16_bf16, smallest terms first.  Measured error per element
 // <= 3.4e-7 of sum_k |a_k b_k| (torch's f32 GEMM: 4.6e-7; tests/test_gpu_gemm.py bounds both at
 // 1e-6).  The split runs once per element while the chunk is staged (global f32 -> registers ->
