@@ -890,10 +890,23 @@ int hg_linear_act_tile(int64_t rows, int n, int k);
  *     Y unused); colpart (may be NULL) receives the column sums of C per row tile,
  *     [hg_gemm_colpart_rows(M, tile), N], reduced later in fixed order (hg_colsum_jobs).
  * tile 1..18 = f32-MFMA block tiles (exact f32 products, f32 accumulation, v_mfma_f32_32x32x2_f32);
- * tile 19..28 = the same product on the bf16 matrix cores with every f32 operand split exactly
+ * tile 19..32 = the same product on the bf16 matrix cores with every f32 operand split exactly
  * into three bf16 terms and the six products of total order <= 2 accumulated in f32
  * (v_mfma_f32_32x32x16_bf16; error per element below torch's f32 GEMM's, csrc/hg_gemm.hip);
- * hg_gemm_tile picks one.  Rows of A, B, C 4-byte aligned (16-byte rows take the vector-load
+ * tile 40..54 = the weight gradient's k_wgrad_tr tiles.  hg_gemm_tile picks one.  Of 19..32, the
+ * tiles 29..32 are forms of the image entries only (29: tile 23 with A's loads two chunks ahead;
+ * 30, 31, 32: tiles 25, 22, 21 at more waves per SIMD); an entry without images that takes them
+ * runs 23, 25, 22, 21 in their place, the same bits.  The ids each entry takes, anything else
+ * HG_ERR_ARG before any launch:
+ *   hg_gemm_f32 modes 0, 1                            1..32
+ *   hg_gemm_f32 mode 3                                19..32
+ *   hg_gemm_f32_wgrad                                 19..28; 40..54 with kmajor 0 only
+ *   hg_gemm_f32_splitk, hg_gemm_f32_splitk_partials   20..28
+ *   hg_gemm_f32_img, hg_gemm_f32_img_split            19..32
+ *   hg_gemm_wgrad_img                                 19..29
+ *   hg_gemm_f32_splitk_img                            19..32 except 24, 26, 29
+ *   hg_gemm_colpart_rows                              1..32, else -1
+ * Rows of A, B, C 4-byte aligned (16-byte rows take the vector-load
  * staging).  One launch, no host synchronisation. */
 int hg_gemm_f32(int mode, const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, const float* Y,
                 int64_t ldY, float* C, int64_t ldc, float* colpart, int64_t M, int N, int K, int act, int tile,
@@ -904,11 +917,11 @@ int hg_gemm_tile(int mode, int64_t M, int N, int K);
  * sum_{k in slice s} A(m, k) B(n, k), with kmajor 0: A [K, M] (lda), B [K, N] (ldb) (the row-major
  * activations / gradients themselves), kmajor 1: A [M, K], B [N, K] (their transposes) — the
  * slices summed later in fixed order (hg_colsum_jobs).  tile 19..28 (the bf16-split kernels of
- * hg_gemm_f32). */
+ * hg_gemm_f32) or, kmajor 0 only, 40..54 (k_wgrad_tr). */
 int hg_gemm_f32_wgrad(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc,
                       int64_t cstride, int64_t M, int N, int64_t K, int slices, int kmajor, int tile, void* stream);
 int64_t hg_gemm_colpart_rows(int64_t M, int tile);
-/* Operand images of the bf16-split tiles (19..28): an f32 operand X with `rows` rows (the
+/* Operand images of the bf16-split tiles (19..32): an f32 operand X with `rows` rows (the
  * product's M or N side) and reduction length K, split once into the three exact bf16 terms and
  * stored in the kernels' LDS fragment order (16-deep k chunks, count rounded up to even; three
  * planes; rows padded to a multiple of 256; zero past rows / K; csrc/hg_gemm.hip), so a GEMM block
